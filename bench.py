@@ -426,6 +426,26 @@ def config5_legs(device, peak_tflops, steps=10, warmup=3, B=32, C=750):
     return out
 
 
+DUMP_SAMPLE = 1 << 21          # elements per sampled flat buffer: 8 MB of float32 each
+
+
+def dump_outputs(out_dir, summary, model):
+    """What the last timed step handed back to its caller, as DIR/<name>.npy: every loss-summary value (float64) and the
+    state the step updated -- parameters, gradients, BatchNorm running statistics -- as float32 samples at fixed positions
+    (seeded, sorted; the whole buffer when it is smaller).  Two builds run with the same arguments compare file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k in summary:
+        np.save(os.path.join(out_dir, "summary_%s.npy" % k), np.asarray([float(summary[k])], dtype=np.float64))
+    for name, buf in (("params", model._flat_params), ("grads", model._flat_grads), ("buffers", model._flat_buffers)):
+        n = buf.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+            vals = buf[torch.from_numpy(idx).to(buf.device)]
+        else:
+            vals = buf
+        np.save(os.path.join(out_dir, "%s_sample.npy" % name), vals.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -448,9 +468,14 @@ def main():
                     "MultiModalImageSoftmaxEngine); reference models/ieee3modalPart.py:312-314, engine/image/softmax.py:81-132")
     ap.add_argument("--no-config5", action="store_true", help="skip the config-5 object of the default N = 1 line (5 short legs "
                     "at 750 classes, 32 triples)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed "
+                    "(its loss summary and a fixed, seeded sample of the updated parameters, gradients and BatchNorm "
+                    "buffers) as DIR/<name>.npy")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="N > 1 from a plain `python`: seconds the self-started "
                     "ranks get before they are ended and an error line is printed (exit code 124)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1") or 1) == 1:
         # plain `python bench.py --gpus N`: this process becomes the launcher -- N child interpreters, one rank per GPU, with
@@ -568,6 +593,8 @@ def main():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     dt = float(tmax.item())
     value = args.steps * B * world / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, summary, model)
 
     # ---- roofline passes: the same steps with a HIP event pair around every conv launch.  IN SITU (mode 2): the executor's
     # streams stay on -- forward / dgrad pairs on the launch stream, weight-gradient pairs on the side stream -- so a pair

@@ -1,8 +1,9 @@
 #!/bin/bash
 # Builds the reference's own native CMC/mAP evaluator (Cython) from the source
 # where it lies under /root/reference, into oracle/_ref/ (git-ignored AND
-# gpurun-ignored: a reference-derived binary stays in this container; only the
-# CPU test tests/test_evaluator_oracle.py loads it).  Only runs where
+# never committed: a binary derived from the reference stays local; only
+# tests/golden/gen_reference_golden.py loads it, to store its outputs for
+# tests/test_evaluator_oracle.py).  Only runs where
 # /root/reference exists (this container).  The reference's pre-generated
 # rank_cy.c (Cython 0.29.33) does not compile against numpy 2.x
 # ("PyArray_Descr has no member named subarray"), so the .pyx is re-cythonized

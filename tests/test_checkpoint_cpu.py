@@ -84,24 +84,21 @@ def test_imagenet_resnet50_initialises_the_three_backbones(tmp_path, monkeypatch
         build_model("ieee3modalPart", num_classes=C, loss="margin", pretrained=True, device="cpu")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/torchreid"), reason="reference tree not present")
-def test_checkpoints_interoperate_with_the_reference_model(tmp_path):
-    """a checkpoint written here loads into the reference's IEEE3modalPart with its own loader (strict), and one
-    written by the reference loads here: same keys, same shapes, same order"""
-    from oracle.ref_import import import_reference
-    torchreid = import_reference()
+def test_checkpoints_interoperate_with_the_reference_model(tmp_path, golden_dir):
+    """a checkpoint written here loads into the reference's IEEE3modalPart with its own loader (strict: the keys and shapes
+    of its state_dict, tests/golden/state_dict_spec.txt), and one written by the reference (torch.save of its state_dict,
+    keys in its order) loads here: same keys, same shapes, same order"""
+    spec = [l.split() for l in open(os.path.join(golden_dir, "state_dict_spec.txt")) if not l.startswith("#")]
+    ref_shapes = OrderedDict((r[0], tuple(int(v) for v in r[1].split(",")) if len(r) > 1 else ()) for r in spec)
     ours = _model(seed=5)
     with torch.no_grad():
         ours._flat_params.normal_(0, 0.05)
     ckpt.save_checkpoint({"state_dict": ours.state_dict(), "epoch": 1}, str(tmp_path))
-    rm = torchreid.models.build_model("ieee3modalPart", num_classes=C, loss="margin", pretrained=False, use_gpu=False)
     state = torch.load(str(tmp_path / "model.pth.tar-1"), weights_only=False)["state_dict"]
-    rm.load_state_dict(state)                                           # strict: key sets identical
-    assert list(rm.state_dict().keys()) == list(ours.state_dict().keys())
-    with torch.no_grad():
-        for p in rm.parameters():
-            p.mul_(0.5)
-    torch.save({"state_dict": rm.state_dict(), "epoch": 9}, str(tmp_path / "ref.pth"))
+    assert list(state.keys()) == list(ref_shapes.keys())
+    assert all(tuple(v.shape) == ref_shapes[k] for k, v in state.items())
+    ref_state = OrderedDict((k, state[k] * 0.5 if state[k].is_floating_point() else state[k].clone()) for k in ref_shapes)
+    torch.save({"state_dict": ref_state, "epoch": 9}, str(tmp_path / "ref.pth"))
     back = _model(seed=6)
     assert ckpt.resume_from_checkpoint(str(tmp_path / "ref.pth"), back) == 9
     assert torch.equal(back.backbone[1].layer2[0].conv2.weight, ours.backbone[1].layer2[0].conv2.weight * 0.5)

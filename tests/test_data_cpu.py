@@ -120,18 +120,16 @@ def test_continuous_index_stream_ends_every_epoch_where_the_sampler_ends(workers
     del it, dl
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/torchreid"), reason="reference tree not present")
-def test_identity_sampler_reproduces_the_reference_sequence():
-    from oracle.ref_import import import_reference
-    import_reference()
-    from torchreid.data.sampler import RandomIdentitySampler as RefSampler
+def test_identity_sampler_reproduces_the_reference_sequence(golden_dir):
+    """the reference's RandomIdentitySampler on _source(17), batch 16, 4 instances, seeds 0 and 7 (sequences stored by
+    tests/golden/gen_reference_golden.py)"""
+    REF = np.load(os.path.join(golden_dir, "reference_golden.npz"))
     data = _source(n_pid=17)
     for seed in (0, 7):
-        random.seed(seed); np.random.seed(seed)
-        want = list(iter(RefSampler(data, 16, 4)))
+        want = REF["sampler_seed%d" % seed].tolist()
         random.seed(seed); np.random.seed(seed)
         got = list(iter(smp.RandomIdentitySampler(data, 16, 4)))
-        assert got == want and len(smp.RandomIdentitySampler(data, 16, 4)) == len(RefSampler(data, 16, 4))
+        assert got == want and len(smp.RandomIdentitySampler(data, 16, 4)) == int(REF["sampler_len"])
 
 
 def _make_tree(root, names, size=(40, 24)):
@@ -241,14 +239,9 @@ def test_sharded_sampler_slices_the_single_process_batches():
         smp.ShardedIdentitySampler(smp.RandomIdentitySampler(data, 8, 4), 2, 3)      # 2 identities cannot feed 3 ranks
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/torchreid"), reason="reference tree not present")
-def test_sharded_sampler_is_a_slice_of_the_reference_sequence():
-    from oracle.ref_import import import_reference
-    import_reference()
-    from torchreid.data.sampler import RandomIdentitySampler as RefSampler
+def test_sharded_sampler_is_a_slice_of_the_reference_sequence(golden_dir):
     data = _source(n_pid=17)
-    random.seed(3); np.random.seed(3)
-    want = list(iter(RefSampler(data, 16, 4)))
+    want = np.load(os.path.join(golden_dir, "reference_golden.npz"))["sampler_seed3"].tolist()    # the reference's, seed 3
     for r in range(2):
         s = smp.ShardedIdentitySampler(smp.RandomIdentitySampler(data, 16, 4), r, 2)
         random.seed(3); np.random.seed(3)

@@ -1,7 +1,6 @@
 """CPU: the evaluator oracle against the golden vectors captured from the imported reference
-(tests/golden/gen_evaluator_golden.py) and against oracle/_ref (the reference's own Cython
-evaluator) when that has been built."""
-import importlib.util
+(tests/golden/gen_evaluator_golden.py) and against the outputs of the reference's own Cython evaluator
+(tests/golden/gen_reference_golden.py)."""
 import os
 
 import numpy as np
@@ -56,26 +55,27 @@ def test_distmat_oracle_float_tolerance(G):
     np.testing.assert_allclose(ev.cosine_np(q, g), G["F_cos"], rtol=0, atol=1e-6)
 
 
-def test_oracle_vs_reference_native_evaluator():
-    """oracle/_ref/rank_cy*.so is the reference's Cython evaluator built from its own source."""
-    here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref")
-    so = [f for f in (os.listdir(here) if os.path.isdir(here) else []) if f.startswith("rank_cy") and f.endswith(".so")]
-    if not so:
-        pytest.skip("oracle/_ref not built (needs /root/reference; see oracle/build_ref.sh)")
-    spec = importlib.util.spec_from_file_location("rank_cy", os.path.join(here, so[0]))
-    rank_cy = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(rank_cy)
+def rank_problem():
+    """120 queries x 1500 gallery rows, 60 identities, 4 cameras (seeded)"""
     rng = np.random.RandomState(7)
     nq, ng = 120, 1500
     d = (rng.rand(nq, ng) * 20).astype(np.float32)
     qp, gp = rng.randint(0, 60, nq), rng.randint(0, 60, ng)
     qc, gc = rng.randint(0, 4, nq), rng.randint(0, 4, ng)
-    cmc_ref, map_ref = rank_cy.evaluate_cy(d, qp, gp, qc, gc, 20, False)
+    return d, qp, gp, qc, gc
+
+
+def test_oracle_vs_reference_native_evaluator(golden_dir):
+    """the reference's Cython evaluator (rank_cy.pyx, built from its own source) on rank_problem(): its CMC and mAP, stored
+    in tests/golden/reference_golden.npz by tests/golden/gen_reference_golden.py"""
+    R = np.load(os.path.join(golden_dir, "reference_golden.npz"))
+    cmc_ref, map_ref = R["rank_cmc"], float(R["rank_mAP"])
+    d, qp, gp, qc, gc = rank_problem()
     cmc, m_ap = ev.rank_market1501_c(d, qp, gp, qc, gc, 20)
     assert np.array_equal(cmc, cmc_ref)
-    assert abs(m_ap - float(map_ref)) < 1e-6      # the Cython path accumulates AP in float32
+    assert abs(m_ap - map_ref) < 1e-6      # the Cython path accumulates AP in float32
     cmc32, map32 = ev.rank_market1501_c(d, qp, gp, qc, gc, 20, f32_accum=True)
-    assert abs(map32 - float(map_ref)) < 1e-6
+    assert abs(map32 - map_ref) < 1e-6
 
 
 def test_split_pieces_sum_exactly_and_kept_products_are_fp32_grade():
