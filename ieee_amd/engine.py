@@ -121,12 +121,10 @@ class Engine(object):
         the in-loop test call does not pass it on, :217-225)."""
         if visrank and not test_only:
             raise ValueError('visrank can be set to True only if test_only=True')
-        if visrank:
-            raise NotImplementedError('visrank (the cv2 / t-SNE visualisation) is outside the hot path')
         eval_args = dict(dist_metric=dist_metric, normalize_feature=normalize_feature, save_dir=save_dir,
                          use_metric_cuhk03=use_metric_cuhk03, ranks=ranks)
         if test_only:
-            self.test(rerank=rerank, **eval_args)
+            self.test(rerank=rerank, visrank=visrank, visrank_topk=visrank_topk, **eval_args)
             return
         began = time.time()
         self.start_epoch, self.max_epoch = start_epoch, max_epoch
@@ -220,8 +218,9 @@ class Engine(object):
             print('##### Evaluating {} ({}) #####'.format(name, where))
             rank1, mAP = self._evaluate(dataset_name=name, query_loader=loaders['query'],
                                         gallery_loader=loaders['gallery'], dist_metric=dist_metric,
-                                        normalize_feature=normalize_feature, use_metric_cuhk03=use_metric_cuhk03,
-                                        ranks=ranks, rerank=rerank)
+                                        normalize_feature=normalize_feature, visrank=visrank,
+                                        visrank_topk=visrank_topk, save_dir=save_dir,
+                                        use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, rerank=rerank)
             if self.writer is not None:
                 self.writer.add_scalar('Test/{}/rank1'.format(name), rank1, self.epoch)
                 self.writer.add_scalar('Test/{}/mAP'.format(name), mAP, self.epoch)
@@ -271,6 +270,11 @@ class Engine(object):
                   normalize_feature=False, visrank=False, visrank_topk=10, save_dir='', use_metric_cuhk03=False,
                   ranks=[1, 5, 10, 20], rerank=False):
         """descriptors -> distance matrix -> CMC / mAP, printed like engine.py:339-441; returns (rank-1, mAP)"""
+        if visrank and ddp.world_size() > 1:
+            raise RuntimeError('visrank needs the whole distance matrix, which a sharded evaluation over {} ranks never '
+                               'forms: run engine.run(test_only=True, visrank=True) in one process on one GPU '
+                               '(a plain `python` command with WORLD_SIZE unset or 1, not torchrun or '
+                               'ieee_amd.dist.launch)'.format(ddp.world_size()))
         clock = AverageMeter()
         say = print if ddp.rank() == 0 else (lambda *a, **k: None)     # one report, not one per rank
         if ddp.world_size() > 1 and self.model is not None and hasattr(self.model, "_flat_buffers"):
@@ -305,7 +309,30 @@ class Engine(object):
         for r in ranks:
             say('Rank-{:<3}: {:.2%}'.format(r, cmc[r - 1]))     # IndexError when r exceeds the curve, as in the reference
         say('\n')
+        if visrank:     # engine.py:423-431 (commented out there): the ranked figures, from the matrix ranked above
+            self._visrank(distmat, dataset_name, query_loader, gallery_loader, visrank_topk, save_dir)
         return cmc[0], mAP
+
+    def _test_records(self, name, query_loader, gallery_loader):
+        """(query, gallery) records of one test set: the data manager's fetch_test_loaders(name) as torchreid has it,
+        else the loaders' datasets (ieee_amd.data.DeviceLoader keeps them as .dataset.data)"""
+        fetch = getattr(self.datamanager, 'fetch_test_loaders', None)
+        if callable(fetch):
+            return fetch(name)
+        recs = [getattr(getattr(ld, 'dataset', None), 'data', None) for ld in (query_loader, gallery_loader)]
+        if recs[0] is None or recs[1] is None:
+            raise ValueError('visrank needs the query / gallery records of {!r}: give the data manager a '
+                             'fetch_test_loaders(name) or use loaders with a .dataset.data list '
+                             '(ieee_amd.data.build_loaders)'.format(name))
+        return recs[0], recs[1]
+
+    def _visrank(self, distmat, name, query_loader, gallery_loader, topk, save_dir):
+        from .reidtools import visualize_ranked_results
+        dm = self.datamanager
+        visualize_ranked_results(distmat, self._test_records(name, query_loader, gallery_loader),
+                                 getattr(dm, 'data_type', 'image'), width=getattr(dm, 'width', 128),
+                                 height=getattr(dm, 'height', 256), save_dir=osp.join(save_dir, 'visrank_' + name),
+                                 topk=topk)
 
     # ---- small hooks the reference exposes ------------------------------------------------------------------------
     def compute_loss(self, criterion, outputs, targets):

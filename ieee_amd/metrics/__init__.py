@@ -2,3 +2,4 @@
 from .accuracy import accuracy  # noqa: F401
 from .distance import compute_distance_matrix, cosine_distance, euclidean_squared_distance  # noqa: F401
 from .rank import evaluate_rank  # noqa: F401
+from .topk import rank_topk  # noqa: F401

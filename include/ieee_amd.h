@@ -93,6 +93,17 @@ int ieee_rank_market1501_ws(const float* distmat, int64_t ldd, int64_t num_q, in
                             const int32_t* q_pids, const int32_t* g_pids, const int32_t* q_camids,
                             const int32_t* g_camids, int64_t max_rank, double* ap, int32_t* first_pos,
                             int64_t* summary, void* work, int64_t work_bytes, void* stream);
+/* Ranked retrieval: the k nearest gallery entries of every query, what torchreid/utils/reidtools.py:49 gets from
+ * np.argsort(distmat, axis=1) on the host.  distmat [num_q][num_g] fp32 (row stride ldd >= num_g) on the device.
+ * With exclude_same_cam != 0 the four int32 label arrays are read and an entry with the query's identity AND camera is
+ * skipped (reidtools.py:110-112, rank.py:136-137); otherwise they may be null.  Outputs, [num_q][k] row-major:
+ * out_idx int32 gallery indices and out_dist fp32 distances, ascending in (distance, gallery index) -- a stable
+ * argsort of the kept row, -0.0 equal to +0.0, NaN after +inf.  A row with fewer than k kept entries is padded with
+ * idx -1 and dist +inf.  1 <= k <= 1024, else IEEE_ERR_BAD_ARG before any launch.  No workspace, no host sync. */
+int ieee_rank_topk(const float* distmat, int64_t ldd, int64_t num_q, int64_t num_g,
+                   const int32_t* q_pids, const int32_t* g_pids, const int32_t* q_camids,
+                   const int32_t* g_camids, int exclude_same_cam, int64_t k, int32_t* out_idx,
+                   float* out_dist, void* stream);
 
 /* ---- convolution as implicit GEMM over NHWC (MFMA) ------------------------ */
 /* These replace torch's conv2d forward / backward as dispatched by the
