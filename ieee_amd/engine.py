@@ -26,7 +26,8 @@ from torch.nn import functional as F
 
 from . import _lib, dist as ddp
 from .checkpoint import save_checkpoint
-from .losses import CrossEntropyLoss, DeepSupervision, multiModalMarginLossNew
+from .losses import (CrossEntropyLoss, DeepSupervision, chunks_short_of_identities, multiModalMarginLossNew,
+                     target_out_of_range)
 from .meters import AverageMeter, DeferredSummary, MetricMeter
 from .metrics import accuracy, compute_distance_matrix, evaluate_rank
 from .optim import FusedAdam, FusedSGD
@@ -405,14 +406,12 @@ def _is_native(model):
     return hasattr(model, "native_net")
 
 
-def _chunks_short_of_identities(pids):
-    """True when `feat.chunk(n)` yields fewer than n = len(unique(pids)) pieces, i.e. when the reference's 3M loss dies
-    with `IndexError: tuple index out of range` in its first loop (multi_modal_margin_loss_new.py:24-33) BEFORE any
-    gradient exists.  Evaluated on the host so that the same error can be raised before this step touches the weights."""
-    rows = int(pids.numel())
-    n = int(torch.unique(pids).numel())
-    per = -(-rows // n)
-    return -(-rows // per) < n
+def batch_error(pids, weight_m, num_classes):
+    """the exception the reference's step raises in its losses for these labels, or None (host-side: see _guard_batch)"""
+    pids = pids.detach().cpu()
+    if weight_m > 0 and chunks_short_of_identities(pids):
+        return IndexError('tuple index out of range')
+    return target_out_of_range(pids, num_classes)
 
 
 class _FusedStepMixin(object):
@@ -421,21 +420,23 @@ class _FusedStepMixin(object):
     def _fused_ok(self):
         return _is_native(self.model) and isinstance(self.optimizer, (FusedSGD, FusedAdam)) and self.use_gpu
 
-    def _guard_chunks(self, pids, weight_m):
-        """the reference's IndexError, raised where the reference raises it: before backward / the optimizer"""
-        if weight_m <= 0:
-            return
+    def _guard_batch(self, pids, weight_m):
+        """the reference's errors for a batch it cannot train on, raised before this step launches anything: the 3M loss's
+        IndexError when the chunks are short of identities (it runs first, margin.py:107-111), then the cross entropy's
+        RuntimeError for a label outside [0, num_classes) -- the fused step would otherwise read logits[label] out of range"""
         # checked on every batch (64 labels: negligible next to a step); only a caller that declares its batch resident
         # (`engine.resident_batch`, bench.py: the same tensor object every step) gets the answer of the first check --
         # the address / version / shape of a DataLoader batch is NOT an identity: the allocator hands the same block out
         # again for the next batch
-        if self.resident_batch and getattr(self, "_chunk_for", None) is pids:
-            bad = self._chunk_bad
+        if self.resident_batch and getattr(self, "_guard_for", None) is pids:
+            err = self._guard_err
         else:
-            bad = _chunks_short_of_identities(pids)
-            self._chunk_for, self._chunk_bad = (pids if self.resident_batch else None), bad
-        if bad:
-            raise IndexError('tuple index out of range')
+            # the bound is the width of the logits the loss reads: the classifier's, as for the reference's scatter_
+            classes = getattr(self.model, "num_classes", None) or self.datamanager.num_train_pids
+            err = batch_error(pids, weight_m, classes)
+            self._guard_for, self._guard_err = (pids if self.resident_batch else None), err
+        if err is not None:
+            raise err
 
     def _fused_step(self, imgs, pids, weight_x, weight_m, margin, eps, total_rows=None):
         lib = _lib.require_gpu()
@@ -728,7 +729,7 @@ class Image3MEngine(_FusedStepMixin, Engine):
         self._sync_replicas_once()
         data, total_rows = self._local_batch(data)
         imgs, pids, timeids = self.parse_data_for_train(data)
-        self._guard_chunks(pids, self.weight_m)
+        self._guard_batch(pids, self.weight_m)
         imgs, pids = self._to_device(imgs, pids, data.get('pid_dev') if isinstance(data, dict) else None)
         if self._fused_ok():
             small, out3 = self._fused_step(imgs, pids, self.weight_x, self.weight_m, self.margin, self.criterion_x.eps,
@@ -776,6 +777,7 @@ class MultiModalImageSoftmaxEngine(_FusedStepMixin, Engine):
         self._sync_replicas_once()
         data, total_rows = self._local_batch(data)
         imgs, pids, timeids = self.parse_data_for_train(data)
+        self._guard_batch(pids, 0)
         imgs, pids = self._to_device(imgs, pids, data.get('pid_dev') if isinstance(data, dict) else None)
         if self._fused_ok():
             small, _ = self._fused_step(imgs, pids, 1.0, 0.0, 0.0, self.criterion.eps, total_rows)

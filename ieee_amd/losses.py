@@ -7,6 +7,28 @@ from torch import nn
 from . import _lib
 
 
+def chunks_short_of_identities(pids):
+    """True when `feat.chunk(n)` yields fewer than n = len(unique(pids)) pieces, i.e. when the reference's 3M loss dies
+    with `IndexError: tuple index out of range` in its first loop (multi_modal_margin_loss_new.py:24-33) BEFORE any
+    gradient exists.  Evaluated on the host so that the same error can be raised before anything is launched."""
+    rows = int(pids.numel())
+    n = int(torch.unique(pids).numel())
+    per = -(-rows // n)
+    return -(-rows // per) < n
+
+
+def target_out_of_range(targets, num_classes):
+    """The RuntimeError the reference's cross entropy raises for a label outside [0, num_classes) -- its one-hot is a
+    host-side `scatter_` (cross_entropy_loss.py:45-46) -- or None.  ce_rows_kernel reads logits[target] unchecked, so
+    this runs on the host before the launch."""
+    t = targets.detach().reshape(-1)
+    bad = (t < 0) | (t >= num_classes)
+    if not bool(bad.any()):
+        return None
+    v = int(t[bad][0])
+    return RuntimeError("index %d is out of bounds for dimension 1 with size %d" % (v, num_classes))
+
+
 class _CEFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets, eps):
@@ -50,6 +72,9 @@ class CrossEntropyLoss(nn.Module):
 
     def forward(self, inputs, targets):
         assert inputs.dim() == 2 and inputs.size(1) == self.num_classes
+        err = target_out_of_range(targets.cpu(), self.num_classes)   # the reference moves the targets to the host too
+        if err is not None:
+            raise err
         return _CEFunction.apply(inputs, targets, self.eps)
 
 
@@ -88,6 +113,8 @@ class multiModalMarginLossNew(nn.Module):
         self.margin = margin
 
     def forward(self, feat1, feat2, feat3, label1):
+        if chunks_short_of_identities(label1.cpu()):
+            raise IndexError('tuple index out of range')     # the reference's loop over the chunks (:24-33)
         return _MarginFunction.apply(feat1, feat2, feat3, label1, self.margin)
 
 
