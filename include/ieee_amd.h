@@ -536,11 +536,30 @@ int ieee_adam_step(float* params, const float* grads, float* exp_avg, float* exp
 /* ---- re-ranking ----------------------------------------------- */
 /* k-reciprocal re-ranking, torchreid/utils/rerank.py:31-113 (engine/engine.py:402-406): device matrices
  * q_g_dist [Q][G], q_q_dist [Q][Q], g_g_dist [G][G] fp32 -> out [Q][G] fp32.  Dense like the reference (three
- * (Q+G)^2 fp32 work matrices: Q+G < 46000); rank ties are broken by index.  k1+1 <= 64. */
+ * (Q+G)^2 fp32 work matrices: Q+G < 46000); rank ties are broken by index.  k1+1 <= 64.
+ * For Q+G >= 46000 use ieee_rerank_sparse below: same arguments, same output bits, no (Q+G)^2 workspace. */
 int64_t ieee_rerank_workspace_bytes(int64_t Q, int64_t G, int64_t k1);
 int ieee_rerank(const float* q_g_dist, const float* q_q_dist, const float* g_g_dist, int64_t Q, int64_t G,
                 int64_t k1, int64_t k2, double lambda_value, float* out, void* work, int64_t work_bytes,
                 void* stream);
+/* The same re-ranking in sparse form: the same arguments and bit-identical output to ieee_rerank wherever that runs,
+ * with no N x N workspace (N = Q+G).  Bounds: Q, G >= 1, 1 <= k1 <= 63, k1+1 <= N < 2^31, 1 <= k2 <= k1+1.  The
+ * inputs are read in two streaming passes (column maxima, then the k1+1 nearest of every column); the k-reciprocal
+ * weights V and their query expansion Vq are stored as sparse rows, and the Jaccard sum walks an inverted index.
+ * Workspace contract: ieee_rerank_sparse_workspace_bytes(Q, G, k1, k2) is a data-independent upper bound (no host
+ * read-back, no allocation in the library): rows of V hold at most min(K(1+Kh), N) entries, rows of Vq at most
+ * min(k2 K(1+Kh), N), K = k1+1, Kh = round_half_even(k1/2)+1.  It returns -1 (and sets the error text) for arguments
+ * out of range.  About 2.8 GB at Q = 10000, G = 100000, k1 = 20, k2 = 6.  Inputs are taken to be finite; any bits
+ * are memory-safe. */
+int64_t ieee_rerank_sparse_workspace_bytes(int64_t Q, int64_t G, int64_t k1, int64_t k2);
+int ieee_rerank_sparse(const float* q_g_dist, const float* q_q_dist, const float* g_g_dist, int64_t Q, int64_t G,
+                       int64_t k1, int64_t k2, double lambda_value, float* out, void* work, int64_t work_bytes,
+                       void* stream);
+/* Where the intermediates of ieee_rerank_sparse lie in its workspace, for inspection after a call: fields[11] =
+ * {K, capV, capVq, then byte offsets of rank [N][K] int32, V counts [N] int32, V columns [N][capV] int32, V values
+ * [N][capV] fp32, Vq counts, Vq columns [N][capVq], Vq values, column maxima [N] (bits of fp32)}.  Vq is absent
+ * (capVq = 0) when k2 = 1.  Row r of V holds counts[r] entries in ascending column order. */
+int ieee_rerank_sparse_layout(int64_t Q, int64_t G, int64_t k1, int64_t k2, int64_t* fields);
 
 /* ---- input pipeline ------------------------------------------ */
 /* The reference's per-image chain Resize((Ho,Wo)) -> RandomHorizontalFlip -> ToTensor -> Normalize
