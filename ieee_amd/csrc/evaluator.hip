@@ -37,6 +37,7 @@ struct DistEpi {
   const float* gsc;
   int nt;             // non-temporal stores (outputs beyond the 256 MB of MALL: 4.8 instead of 4.0 TB/s)
   __device__ __forceinline__ float value(float v, float a, float b) const {
+    if (metric == 2) return -v;                     // negated inner product (gnn_rerank.hip): a, b are not looked at
     return metric == 0 ? (a + b) + (-2.0f * v)      // distance.py:62-63
                        : 1.0f - v * a * b;          // distance.py:77-79 (a, b hold 1/max(|.|,eps))
   }
@@ -765,7 +766,7 @@ extern "C" int ieee_sqeuclid_distmat(const void* q, const void* g, int64_t m, in
   IEEE_REQUIRE(m > 0 && n > 0 && d > 0, "distmat: empty input (m=%ld n=%ld d=%ld)", (long)m, (long)n, (long)d);
   IEEE_REQUIRE(d % 8 == 0, "distmat: feature dim %ld must be a multiple of 8", (long)d);
   IEEE_REQUIRE(ldo >= n, "distmat: ldo < n");
-  IEEE_REQUIRE(metric == 0 || metric == 1, "distmat: unknown metric %d", metric);
+  IEEE_REQUIRE(metric >= 0 && metric <= 2, "distmat: unknown metric %d", metric);
   IEEE_REQUIRE(m < (1ll << 31) && n < (1ll << 31), "distmat: too many rows");
   hipStream_t st = (hipStream_t)stream;
   float* qn = (float*)work;
@@ -778,13 +779,17 @@ extern "C" int ieee_sqeuclid_distmat(const void* q, const void* g, int64_t m, in
     attr_done = true;
   }
   if (dtype == IEEE_F32) {
-    rownorm_kernel<float><<<cdiv(m, 4), 256, 0, st>>>((const float*)q, m, (int)d, metric, qn);
-    rownorm_kernel<float><<<cdiv(n, 4), 256, 0, st>>>((const float*)g, n, (int)d, metric, gn);
+    if (metric != 2) {   // metric 2 has no norms: the epilogue loads whatever work holds and drops it
+      rownorm_kernel<float><<<cdiv(m, 4), 256, 0, st>>>((const float*)q, m, (int)d, metric, qn);
+      rownorm_kernel<float><<<cdiv(n, 4), 256, 0, st>>>((const float*)g, n, (int)d, metric, gn);
+    }
     distmat_kernel<float><<<tiles_m * tiles_n, 256, smem, st>>>((const float*)q, (const float*)g, qn, gn, out, (int)m,
                                                                 (int)n, (int)d, ldo, metric, tiles_m, tiles_n);
   } else if (dtype == IEEE_BF16) {
-    rownorm_kernel<bf16><<<cdiv(m, 4), 256, 0, st>>>((const bf16*)q, m, (int)d, metric, qn);
-    rownorm_kernel<bf16><<<cdiv(n, 4), 256, 0, st>>>((const bf16*)g, n, (int)d, metric, gn);
+    if (metric != 2) {
+      rownorm_kernel<bf16><<<cdiv(m, 4), 256, 0, st>>>((const bf16*)q, m, (int)d, metric, qn);
+      rownorm_kernel<bf16><<<cdiv(n, 4), 256, 0, st>>>((const bf16*)g, n, (int)d, metric, gn);
+    }
     distmat_kernel<bf16><<<tiles_m * tiles_n, 256, smem, st>>>((const bf16*)q, (const bf16*)g, qn, gn, out, (int)m,
                                                                (int)n, (int)d, ldo, metric, tiles_m, tiles_n);
   } else {
@@ -813,7 +818,7 @@ extern "C" int ieee_sqeuclid_distmat_split(const float* q, const float* g, int64
   const int terms = split_terms(scheme);
   IEEE_REQUIRE(terms != 0, "distmat_split: unknown scheme %ld (IEEE_SPLIT_BF16X3 / _BF16X2 / _F16X2)", (long)scheme);
   IEEE_REQUIRE(ldo >= n, "distmat_split: ldo < n");
-  IEEE_REQUIRE(metric == 0 || metric == 1, "distmat_split: unknown metric %d", metric);
+  IEEE_REQUIRE(metric >= 0 && metric <= 2, "distmat_split: unknown metric %d", metric);
   IEEE_REQUIRE(m < (1ll << 31) && n < (1ll << 31) && terms * d < (1ll << 31), "distmat_split: too large");
   IEEE_REQUIRE(work_bytes >= ieee_sqeuclid_distmat_split_workspace_bytes(m, n, d, scheme),
                "distmat_split: workspace of %ld bytes is too small", (long)work_bytes);
@@ -825,8 +830,10 @@ extern "C" int ieee_sqeuclid_distmat_split(const float* q, const float* g, int64
   char* qs = (char*)work + split_align((m + n) * 8);
   char* gs = qs + split_align(m * terms * d * 2);
   // row norms from the fp32 rows themselves (exactly as the fp32 path)
-  rownorm_kernel<float><<<cdiv(m, 4), 256, 0, st>>>(q, m, (int)d, metric, qn);
-  rownorm_kernel<float><<<cdiv(n, 4), 256, 0, st>>>(g, n, (int)d, metric, gn);
+  if (metric != 2) {
+    rownorm_kernel<float><<<cdiv(m, 4), 256, 0, st>>>(q, m, (int)d, metric, qn);
+    rownorm_kernel<float><<<cdiv(n, 4), 256, 0, st>>>(g, n, (int)d, metric, gn);
+  }
   const int tiles_m = cdiv(m, 128), tiles_n = cdiv(n, 128);
   static bool attr_done = false;
   if (!attr_done) {

@@ -40,6 +40,12 @@ def _hms(seconds):
     return str(datetime.timedelta(seconds=int(seconds)))
 
 
+def _check_rerank(rerank):
+    """rerank is False / True (k-reciprocal) or the string 'gnn'; values that are not strings keep their truthiness"""
+    if isinstance(rerank, str) and rerank != 'gnn':
+        raise ValueError("rerank must be False, True (k-reciprocal re-ranking) or 'gnn', got {!r}".format(rerank))
+
+
 class Engine(object):
     """Base driver.  Subclasses set self.model / optimizer / scheduler, register them and implement
     forward_backward(data) -> dict of scalars."""
@@ -116,16 +122,20 @@ class Engine(object):
     # ---- the loop ------------------------------------------------------------------------------------------------
     def run(self, save_dir='log', max_epoch=0, start_epoch=0, print_freq=10, fixbase_epoch=0, open_layers=None,
             start_eval=0, eval_freq=-1, test_only=False, dist_metric='euclidean', normalize_feature=False,
-            visrank=False, visrank_topk=10, use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False):
+            visrank=False, visrank_topk=10, use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False,
+            rerank_k1=26, rerank_k2=7):
         """engine.py:126-232.  As in the reference there is NO evaluation or checkpoint after the last epoch (the
         `(epoch + 1) != max_epoch` guard, :216), and re-ranking applies to test_only runs (its docstring, :171-172;
-        the in-loop test call does not pass it on, :217-225)."""
+        the in-loop test call does not pass it on, :217-225).  rerank: False, True (k-reciprocal) or 'gnn' (see test;
+        rerank_k1 / rerank_k2 belong to 'gnn' alone)."""
         if visrank and not test_only:
             raise ValueError('visrank can be set to True only if test_only=True')
+        _check_rerank(rerank)
         eval_args = dict(dist_metric=dist_metric, normalize_feature=normalize_feature, save_dir=save_dir,
                          use_metric_cuhk03=use_metric_cuhk03, ranks=ranks)
         if test_only:
-            self.test(rerank=rerank, visrank=visrank, visrank_topk=visrank_topk, **eval_args)
+            self.test(rerank=rerank, rerank_k1=rerank_k1, rerank_k2=rerank_k2, visrank=visrank,
+                      visrank_topk=visrank_topk, **eval_args)
             return
         began = time.time()
         self.start_epoch, self.max_epoch = start_epoch, max_epoch
@@ -210,8 +220,14 @@ class Engine(object):
 
     # ---- evaluation ----------------------------------------------------------------------------------------------
     def test(self, dist_metric='euclidean', normalize_feature=False, visrank=False, visrank_topk=10, save_dir='',
-             use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False):
-        """every target dataset in turn (engine.py:287-337); returns the last one's mAP like the reference"""
+             use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7):
+        """every target dataset in turn (engine.py:287-337); returns the last one's mAP like the reference.
+        rerank: False; True = k-reciprocal re-ranking (engine.py:402-406); 'gnn' = GNN re-ranking
+        (ieee_amd.rerank.gnn_distmat with rerank_k1, rerank_k2, which the k-reciprocal branch ignores).  The GNN step is
+        always handed L2-normalised descriptors, F.normalize(., p=2, dim=1), whatever dist_metric and normalize_feature
+        say: the method ranks by the raw inner product and the reference's driver feeds it normalised rows.  Any other
+        string raises ValueError; other values keep their truthiness."""
+        _check_rerank(rerank)
         self.set_model_mode('eval')
         mAP = 0.0
         for name, loaders in self.test_loader.items():
@@ -221,7 +237,8 @@ class Engine(object):
                                         gallery_loader=loaders['gallery'], dist_metric=dist_metric,
                                         normalize_feature=normalize_feature, visrank=visrank,
                                         visrank_topk=visrank_topk, save_dir=save_dir,
-                                        use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, rerank=rerank)
+                                        use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, rerank=rerank,
+                                        rerank_k1=rerank_k1, rerank_k2=rerank_k2)
             if self.writer is not None:
                 self.writer.add_scalar('Test/{}/rank1'.format(name), rank1, self.epoch)
                 self.writer.add_scalar('Test/{}/mAP'.format(name), mAP, self.epoch)
@@ -269,8 +286,9 @@ class Engine(object):
     @torch.no_grad()
     def _evaluate(self, dataset_name='', query_loader=None, gallery_loader=None, dist_metric='euclidean',
                   normalize_feature=False, visrank=False, visrank_topk=10, save_dir='', use_metric_cuhk03=False,
-                  ranks=[1, 5, 10, 20], rerank=False):
+                  ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7):
         """descriptors -> distance matrix -> CMC / mAP, printed like engine.py:339-441; returns (rank-1, mAP)"""
+        _check_rerank(rerank)
         if visrank and ddp.world_size() > 1:
             raise RuntimeError('visrank needs the whole distance matrix, which a sharded evaluation over {} ranks never '
                                'forms: run engine.run(test_only=True, visrank=True) in one process on one GPU '
@@ -297,7 +315,11 @@ class Engine(object):
             cmc, mAP = ddp.sharded_evaluate_rank(qf, gf, q_pids, g_pids, q_camids, g_camids, metric=dist_metric)
         else:
             distmat = compute_distance_matrix(qf, gf, dist_metric)
-            if rerank:  # engine.py:402-406: k-reciprocal re-ranking with the query-query and gallery-gallery matrices
+            if rerank == 'gnn':     # GPU-Re-Ranking/gnn_reranking.py on normalised descriptors, as its driver feeds it
+                say('Applying person re-ranking ... (gnn)')
+                from .rerank import gnn_distmat
+                distmat = gnn_distmat(F.normalize(qf, p=2, dim=1), F.normalize(gf, p=2, dim=1), rerank_k1, rerank_k2)
+            elif rerank:  # engine.py:402-406: k-reciprocal re-ranking with the query-query and gallery-gallery matrices
                 say('Applying person re-ranking ...')
                 from .rerank import re_ranking
                 distmat = re_ranking(distmat, compute_distance_matrix(qf, qf, dist_metric),

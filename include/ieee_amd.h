@@ -51,7 +51,8 @@ int ieee_device_is_gfx950(void);
  * chain) or IEEE_BF16 (inputs already bf16; fp32 accumulate).  out [m][n] fp32,
  * row stride ldo elements.  d % 8 == 0.  work: >= (m+n)*4 bytes of scratch
  * (row norms).  metric: 0 euclidean, 1 cosine (distance.py:67-80: rows are
- * L2-normalised with eps 1e-12 and out = 1 - q^.g^). */
+ * L2-normalised with eps 1e-12 and out = 1 - q^.g^), 2 negated inner product
+ * (out = -q_i.g_j, no norms: what ieee_gnn_rerank ranks). */
 int ieee_sqeuclid_distmat(const void* q, const void* g, int64_t m, int64_t n, int64_t d, int dtype,
                           int metric, float* out, int64_t ldo, void* work, void* stream);
 /* the same matrix from fp32 rows on the 16-bit matrix cores: every value is split into 16-bit pieces that sum to it
@@ -560,6 +561,26 @@ int ieee_rerank_sparse(const float* q_g_dist, const float* q_q_dist, const float
  * [N][capV] fp32, Vq counts, Vq columns [N][capVq], Vq values, column maxima [N] (bits of fp32)}.  Vq is absent
  * (capVq = 0) when k2 = 1.  Row r of V holds counts[r] entries in ascending column order. */
 int ieee_rerank_sparse_layout(int64_t Q, int64_t G, int64_t k1, int64_t k2, int64_t* fields);
+/* GNN re-ranking, torchreid/utils/GPU-Re-Ranking/gnn_reranking.py:27-59 with its build_adjacency_matrix and
+ * gnn_propagate kernels: device features xq [Q][d], xg [G][d] fp32 (d % 8 == 0, nothing is normalised here) ->
+ * out [Q][G] fp32 = 1 - sim, sim the cosine of the rows that two rounds of propagation leave, so that ascending out is
+ * the reference's descending similarity.  With X_u = [xq; xg], N = Q + G: score = X_u X_u^T, (S, rank) = its k1 largest
+ * per row; A = B + B^T with B[i][rank[i][j]] = 1; twice: A[i] = sum_{j<k2} S[i][j]^2 A[rank[i][j]] (j ascending, no
+ * atomics: bitwise reproducible), rows L2-normalised and A + A^T formed between the rounds.  k2 = 1: out = 1 - (number
+ * of shared k1-neighbours)/k1.  Defined where the reference is not: ties in rank are broken by the smaller index, and
+ * a row of norm 0 gives similarity 0 (eps 1e-12), not NaN.  Bounds: Q, G >= 1, 1 <= k1 <= min(1024, N), 1 <= k2 <= k1,
+ * else IEEE_ERR_BAD_ARG before any launch.  precision: 0 = fp32 MFMA, or IEEE_SPLIT_* for the two GEMMs (the scores
+ * and the final product).  Workspace: two N x ld fp32 matrices (ld = N rounded up to 8), the two [N][k1] lists, [N]
+ * row sums and the distance GEMM's scratch; ieee_gnn_rerank_workspace_bytes returns -1 (and sets the error text) for
+ * arguments out of range.  Caller-owned memory, everything on `stream`, no host sync. */
+int64_t ieee_gnn_rerank_workspace_bytes(int64_t Q, int64_t G, int64_t d, int64_t k1, int64_t k2, int precision);
+int ieee_gnn_rerank(const float* xq, const float* xg, int64_t Q, int64_t G, int64_t d, int64_t k1, int64_t k2,
+                    int precision, float* out, void* work, int64_t work_bytes, void* stream);
+/* Where ieee_gnn_rerank keeps its intermediates, for inspection after a call: fields[7] = {ld, then byte offsets of
+ * rank [N][k1] int32, S [N][k1] fp32 (the NEGATED scores, not squared: the propagation squares them as it loads),
+ * row sums of squares [N] fp32 (of the last propagation), matrix M0 [N][ld], matrix M1 [N][ld], and the matrix whose
+ * rows fed the final product (M1, the unnormalised second round; M0 = the binary B when k2 = 1)}. */
+int ieee_gnn_rerank_layout(int64_t Q, int64_t G, int64_t d, int64_t k1, int64_t k2, int precision, int64_t* fields);
 
 /* ---- input pipeline ------------------------------------------ */
 /* The reference's per-image chain Resize((Ho,Wo)) -> RandomHorizontalFlip -> ToTensor -> Normalize
