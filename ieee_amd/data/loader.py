@@ -2,9 +2,11 @@
 process with workers=0, configs/RGBNT_ieee_part_margin.yaml:13); the decoded bytes are resized / flipped / normalised on
 the GPU per batch.  Yields the reference's batch dict: {'img': [RGB, NI, TI] float tensors [B,3,H,W] (on the device),
 'pid', 'camid', 'impath', 'timeid'} (data/datasets/dataset.py:344-351)."""
+import collections
 import multiprocessing
 import os
 import queue
+import random
 import sys
 import threading
 
@@ -110,15 +112,19 @@ class _SlotSampler(object):
     A pass ends where the inner batch sampler ENDS, not after len() batches: RandomIdentitySampler's length is an upper bound
     (it stops once fewer than P identities have a group left, data/sampler.py), so every pass is followed by an END marker
     (slot -1) that travels through the workers in order and tells the consumer where the epoch stops (`epoch_items`) -- the
-    epoch boundaries, the optimizer steps per epoch and which pass a batch comes from are the non-continuous loader's."""
+    epoch boundaries, the optimizer steps per epoch and which pass a batch comes from are the non-continuous loader's.
+    on_pass: called before every pass of a continuous stream draws its order (DeviceLoader forks the pass's augmentation
+    generator there, see DeviceLoader._fork_plan_rng)."""
     END = (-1, [])
 
-    def __init__(self, batches, slots, continuous=False):
-        self.batches, self.slots, self.k, self.continuous = batches, slots, 0, continuous
+    def __init__(self, batches, slots, continuous=False, on_pass=None):
+        self.batches, self.slots, self.k, self.continuous, self.on_pass = batches, slots, 0, continuous, on_pass
 
     def __iter__(self):
         while True:
             n = 0
+            if self.continuous and self.on_pass is not None:
+                self.on_pass()
             for idx in self.batches:
                 yield (self.k % self.slots, list(idx))
                 self.k += 1
@@ -166,6 +172,7 @@ class DeviceLoader(object):
         self.rank, self.world = int(rank), int(world)
         self.global_rows = global_rows
         self.batch_size = int(batch_size)
+        self._plan_rngs = collections.deque()     # one generator per pass for the crop / erase draws (_fork_plan_rng), oldest first
         # persistent: keep the worker processes between epochs (the train loader: an epoch of RGBNT201 is a few hundred batches,
         # respawning W processes that import torch at every epoch costs seconds).  Off for the query / gallery loaders: their
         # workers would sit resident -- 2 x W processes preloaded with torch -- through the whole run for one pass per evaluation.
@@ -214,7 +221,7 @@ class DeviceLoader(object):
         # in the consumer's thread, in step with the other ranks)
         self._continuous = os.environ.get("IEEE_LOADER_CONTINUOUS", "1") != "0" and not hasattr(base, "prepare")
         self._it, self._epoch_pos = None, 0
-        self._slot_sampler = _SlotSampler(batches, slots, continuous=self._continuous)
+        self._slot_sampler = _SlotSampler(batches, slots, continuous=self._continuous, on_pass=self._fork_plan_rng)
         self.loader = DataLoader(_SlotDataset(self.dataset, ring), batch_size=None, sampler=self._slot_sampler, num_workers=workers,
                                  collate_fn=_identity, pin_memory=False, persistent_workers=True,
                                  multiprocessing_context=_worker_context(workers))
@@ -229,6 +236,17 @@ class DeviceLoader(object):
                 self._ring_registered = False
         except Exception:
             pass
+
+    def _fork_plan_rng(self):
+        """The crop and erase decisions come from python's `random`, which the identity sampler draws the epoch's order from
+        as well -- and the continuous ring path draws the NEXT epoch's order while this epoch's batches are still being
+        augmented.  So the augmentation draws of a pass do not come from the global generator itself: when a pass begins,
+        BEFORE the sampler draws its order, ONE number is taken from the global generator and seeds a random.Random of the
+        pass's own.  The global stream then reads fork, order, fork, order, ... whatever the prefetch depth (prefetch = 0 and
+        prefetch = k give the same batches bit for bit), and nothing races on a generator.  Only with 'random_crop' or
+        'random_erase' enabled: the flip-only loader leaves `random` to the sampler alone, as before."""
+        if getattr(self.transform, "needs_py_rng", False):
+            self._plan_rngs.append(random.Random(random.getrandbits(64)))
 
     @property
     def sharded(self):
@@ -337,6 +355,7 @@ class DeviceLoader(object):
 
         def one_epoch():
             if self._it is None or self._epoch_pos != 0:
+                self._plan_rngs.clear()          # (a fresh stream forks afresh: drop what the abandoned one left)
                 self._it = iter(self.loader)
             self._epoch_pos = 0
             for k, item in enumerate(epoch_items(self._it)):      # up to the sampler's REAL end of pass (its marker)
@@ -347,6 +366,11 @@ class DeviceLoader(object):
 
     def _batches(self):
         sampler = getattr(self, "loader_base_sampler", None) if self.ring is not None else getattr(self.loader, "sampler", None)
+        augments = getattr(self.transform, "augments", False)        # stages beyond the flip: the plan path
+        if not (self.ring is not None and getattr(self, "_continuous", False)):
+            self._plan_rngs.clear()
+            self._fork_plan_rng()                # (the continuous stream forks in _SlotSampler, where its passes begin)
+        plan_rng = None
         if hasattr(sampler, "prepare"):          # rank-sharded identity sampler: draw / exchange the epoch's order here, in
             sampler.prepare()                    # the main process, not at the DataLoader's first prefetch
         lo, hi = getattr(sampler, "lo", None), getattr(sampler, "hi", None)
@@ -359,8 +383,19 @@ class DeviceLoader(object):
                 batch.pop('slot'), batch.pop('rows')
             stacked = bool(raw) and torch.is_tensor(raw[0])          # [modality] -> [B, H, W, 3] (see _collate)
             n, mods = (int(raw[0].shape[0]), len(raw)) if stacked else (len(raw), len(raw[0]))
+            if augments:
+                # the whole plan (flip, crop, jitter, erase) where the flips alone are drawn below, in the same order:
+                # sample-major, modality-minor, and for a shard the plan of the WHOLE global batch, of which rows lo:hi stay
+                if k == 0 and getattr(self.transform, "needs_py_rng", False):
+                    plan_rng = self._plan_rngs.popleft()             # this pass's generator (_fork_plan_rng)
+                shard = self.global_rows is not None and lo is not None and hi - lo == n
+                rows = int(self.global_rows) if shard else n
+                plan = self.transform.draw_plan(rows * mods, py_rng=plan_rng)
+                index = np.arange(rows * mods).reshape(rows, mods)[lo:hi] if shard else np.arange(n * mods).reshape(n, mods)
+                batch['img'] = [self.transform(raw[m] if stacked else [raw[i][m] for i in range(n)], plan=plan[index[:, m]])
+                                for m in range(mods)]
             # the reference transforms sample by sample, modality by modality: draw the flips in that order
-            if self.global_rows is not None and lo is not None and hi - lo == n:
+            elif self.global_rows is not None and lo is not None and hi - lo == n:
                 # a shard of a global batch: draw the flips of the WHOLE global batch -- every rank consumes the same
                 # torch RNG stream, as the single-process loop would -- and keep this shard's rows; ranks seeded alike
                 # (torch.manual_seed, as the reference's set_random_seed does) then augment the global batch exactly
@@ -368,8 +403,9 @@ class DeviceLoader(object):
                 flips = self.transform.draw_flips(int(self.global_rows) * mods).reshape(int(self.global_rows), mods)[lo:hi]
             else:
                 flips = self.transform.draw_flips(n * mods).reshape(n, mods)
-            batch['img'] = [self.transform(raw[m] if stacked else [raw[i][m] for i in range(n)], flips=flips[:, m])
-                            for m in range(mods)]
+            if not augments:
+                batch['img'] = [self.transform(raw[m] if stacked else [raw[i][m] for i in range(n)], flips=flips[:, m])
+                                for m in range(mods)]
             if torch.cuda.is_available() and torch.is_tensor(batch['img'][0]) and batch['img'][0].is_cuda:
                 # the identity labels follow the images to the device on the same stream (pinned, asynchronous): the engine's
                 # own `pids.cuda()` is a blocking copy from pageable memory -- it drains the launch stream every step and the

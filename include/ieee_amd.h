@@ -597,6 +597,29 @@ int ieee_resize_flip_normalize(const uint8_t* src, float* dst, uint8_t* tmp, int
                                int64_t tmp_rows, const uint8_t* flip, const float* mean3, const float* std3,
                                void* stream);
 
+/* The same chain with the reference's other train augmentations (transforms.py:12-106, 283-311), in its order:
+ *   Resize -> flip -> random crop (Random2DTranslation) -> colour jitter (brightness, contrast) -> ToTensor -> Normalize
+ *   -> random erase.
+ * Arguments up to tmp_rows as above.  plan: DEVICE int32 [N][12], one row per image, drawn on the host
+ * (ieee_amd/data/transforms.py, AugmentPlan.pack): {flip, crop flag, x1, y1, jitter order (0: brightness first),
+ * bits of the brightness factor (float), bits of the contrast factor, erase r0, c0, h, w (h = 0: none), 0}; the last
+ * word must arrive 0 and receives the image's integer sum of L (the contrast stage's grey level comes from it).
+ * stages: bit 0 flip, 1 crop, 2 jitter, 3 erase; a stage whose bit is clear costs nothing and its plan words are ignored.
+ * work: work_bytes >= (crop ? 3 : jitter ? 1 : 0) * N*Ho*Wo*3 bytes of device scratch (the flipped uint8 stage image,
+ * the crop's horizontal intermediate, the cropped image), NULL when neither is on.  The crop enlarges the Ho x Wo stage
+ * image to Hbig x Wbig (Pillow bilinear; tables big_* as above for Wo -> Wbig and Ho -> Hbig, both strictly larger) and
+ * keeps the Ho x Wo window at (x1, y1); only that window is computed.  Every pixel step is Pillow's 8-bit arithmetic
+ * (ImageEnhance / Image.blend for the jitter), the float expression is ieee_resize_flip_normalize's, the erase rectangle
+ * is written as mean3[c].  Launches: 2 + (crop or jitter) + 2 * crop with a horizontal resize pass (5 with everything on),
+ * one less without; no host synchronisation, no allocation.  launches: HOST int, receives that count, or NULL. */
+int ieee_augment_normalize(const uint8_t* src, float* dst, uint8_t* tmp, int64_t N, int64_t Hs, int64_t Ws, int64_t Ho,
+                           int64_t Wo, const int32_t* bounds_h, const int32_t* kk_h, int64_t ksize_h,
+                           const int32_t* bounds_v, const int32_t* kk_v, int64_t ksize_v, int64_t ybox_first,
+                           int64_t tmp_rows, int32_t* plan, int stages, uint8_t* work, int64_t work_bytes, int64_t Hbig,
+                           int64_t Wbig, const int32_t* big_bounds_h, const int32_t* big_kk_h, int64_t big_ksize_h,
+                           const int32_t* big_bounds_v, const int32_t* big_kk_v, int64_t big_ksize_v,
+                           const float* mean3, const float* std3, int* launches, void* stream);
+
 /* ---- whole-network executor --------------------------------------------------- */
 /* One handle = IEEE3modalPart (ieee3modalPart.py:286-523) for a fixed batch / image size / dtype.
  * The caller owns three flat fp32 buffers laid out like the reference's state_dict: parameters,

@@ -67,7 +67,8 @@ def _cycle(loader):
             yield batch
 
 
-def measure(workers=(4, 8, 16, 32), steps=40, warm=8, B=64, size=(256, 128), engine=None, device=None, root=None, prefetch=None, rounds=3):
+def measure(workers=(4, 8, 16, 32), steps=40, warm=8, B=64, size=(256, 128), engine=None, device=None, root=None, prefetch=None, rounds=3,
+            transforms='random_flip'):
     """returns the `loader` object of the bench line"""
     import contextlib
     import io
@@ -76,6 +77,8 @@ def measure(workers=(4, 8, 16, 32), steps=40, warm=8, B=64, size=(256, 128), eng
     own_root = root is None
     root = root or tempfile.mkdtemp(prefix="ieee_loader_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     out = {"batch": B, "source_size": "%dx%d" % size, "steps": steps, "per_workers": {}}
+    if transforms != 'random_flip':
+        out["transforms"] = transforms
     try:
         t0 = time.time()
         # 64 identities x 8 triples: an epoch of the identity sampler is 8 batches of 64; the probe cycles over epochs
@@ -110,7 +113,8 @@ def measure(workers=(4, 8, 16, 32), steps=40, warm=8, B=64, size=(256, 128), eng
         for W in workers:
             with contextlib.redirect_stdout(io.StringIO()):
                 kw = {} if prefetch is None else {"prefetch": prefetch}
-                loaders[W], _, _ = build_loaders(ds, height=256, width=128, batch_size_train=B, num_instances=4, workers=W, **kw)
+                loaders[W], _, _ = build_loaders(ds, height=256, width=128, transforms=transforms, batch_size_train=B, num_instances=4,
+                                                 workers=W, **kw)
             it = its[W] = _cycle(loaders[W])
             for _ in range(warm):          # worker start-up, table upload
                 b = next(it)
@@ -173,6 +177,9 @@ if __name__ == "__main__":
     ap.add_argument("--size", default="256x128")
     ap.add_argument("--prefetch", type=int, default=None)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--transforms", default="random_flip", help="comma-separated train augmentations: random_flip, random_crop, "
+                    "color_jitter, random_erase")
     a = ap.parse_args()
     h, w = (int(v) for v in a.size.split("x"))
-    print(json.dumps(measure(tuple(int(v) for v in a.workers.split(",")), steps=a.steps, size=(h, w), prefetch=a.prefetch, rounds=a.rounds), indent=1))
+    print(json.dumps(measure(tuple(int(v) for v in a.workers.split(",")), steps=a.steps, size=(h, w), prefetch=a.prefetch, rounds=a.rounds,
+                             transforms=a.transforms if ',' not in a.transforms else a.transforms.split(',')), indent=1))

@@ -47,6 +47,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--save-dir", default="")
+    ap.add_argument("--transforms", default="random_flip", help="comma-separated train augmentations (the reference's "
+                    "build_transforms names): random_flip, random_crop, color_jitter, random_erase")
     args = ap.parse_args()
 
     if args.gpus > 1 and ddp.env_world()[0] == 1:
@@ -74,8 +76,8 @@ def main():
         if world > 1:
             torch.distributed.barrier()
     dataset = D.RGBNT201(root=root)
-    train, query, gallery = D.build_loaders(dataset, 256, 128, "random_flip", batch_size_train=args.batch, batch_size_test=32,
-                                            num_instances=4, workers=args.workers)
+    train, query, gallery = D.build_loaders(dataset, 256, 128, [t for t in args.transforms.split(",") if t],
+                                            batch_size_train=args.batch, batch_size_test=32, num_instances=4, workers=args.workers)
     dm = DataManager(dataset, train, query, gallery, "RGBNT201", 4)
 
     model = build_model("ieee3modalPart", num_classes=dm.num_train_pids, loss="margin", pretrained=False, use_gpu=True,
