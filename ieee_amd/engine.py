@@ -3,9 +3,9 @@ train :234-282, test :287-337, _evaluate :339-441; engine/image/margin.py:62-154
 11-132 MultiModalImageSoftmaxEngine): same constructor arguments, method names, keyword meaning, printed report and
 loss_summary keys, so scripts/mainMultiModal.py-style callers run unchanged.  What is underneath is this package's own:
 
-  * fused step (native model + FusedSGD / FusedAdam): forward, 18-head cross entropy, 3M, backward, the RCCL gradient
-    all-reduce and the optimizer update are each one native call; no autograd graph and ONE small device->host read
-    per step for the logging dict (the reference synchronises >= 27 times per step).
+  * fused step (native model + FusedSGD / FusedAdam / FusedRMSprop / FusedRAdam): forward, 18-head cross entropy, 3M,
+    backward, the RCCL gradient all-reduce and the optimizer update are each one native call; no autograd graph and
+    ONE small device->host read per step for the logging dict (the reference synchronises >= 27 times per step).
   * generic step (any other torch.optim optimizer): autograd over the same native forward / backward.
   * data parallel (one process per GPU, ieee_amd/dist.py): the step shards the batch on identity boundaries, the
     replicas are synchronised once before the first step, evaluation shards the feature extraction (one all-gather of
@@ -30,7 +30,7 @@ from .losses import (CrossEntropyLoss, DeepSupervision, chunks_short_of_identiti
                      target_out_of_range)
 from .meters import AverageMeter, DeferredSummary, MetricMeter
 from .metrics import accuracy, compute_distance_matrix, evaluate_rank
-from .optim import FusedAdam, FusedSGD
+from .optim import FUSED_OPTIMIZERS, FusedSGD
 
 _Entry = namedtuple("_Entry", "model optim sched")
 _SUMMARY_3M = ('loss', 'LossX', 'LossM', 'accR', 'lossR', 'accN', 'lossN', 'accT', 'lossT')
@@ -440,7 +440,7 @@ class _FusedStepMixin(object):
     """the native train step shared by the 3M and the CE-only engines"""
 
     def _fused_ok(self):
-        return _is_native(self.model) and isinstance(self.optimizer, (FusedSGD, FusedAdam)) and self.use_gpu
+        return _is_native(self.model) and isinstance(self.optimizer, FUSED_OPTIMIZERS) and self.use_gpu
 
     def _guard_batch(self, pids, weight_m):
         """the reference's errors for a batch it cannot train on, raised before this step launches anything: the 3M loss's

@@ -533,6 +533,20 @@ int ieee_grad_unpack_bf16(const void* in_bf16, float* grads, int64_t n, void* st
 int ieee_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
                    int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
                    void* stream);
+/* torch.optim.RMSprop(alpha, eps, weight_decay, momentum, centered=False) as the reference builds it for optim = 'rmsprop'
+ * (torchreid/optim/optimizer.py:140-147; it passes `momentum` through, eps stays torch's 1e-8) over a flat fp32 range:
+ * g += wd*p; sq = alpha*sq + (1-alpha)*g*g; buf = momentum*buf + g/(sqrt(sq)+eps); p -= lr*buf.  momentum == 0:
+ * momentum_buf may be NULL and p -= lr*g/(sqrt(sq)+eps).  16 bytes per lane when every pointer is 16-byte aligned,
+ * else a scalar form with the same per-element arithmetic.  n < 0 or a NULL pointer: IEEE_ERR_BAD_ARG. */
+int ieee_rmsprop_step(float* params, const float* grads, float* square_avg, float* momentum_buf, int64_t n, float lr,
+                      float alpha, float eps, float weight_decay, float momentum, void* stream);
+/* The reference's own RAdam.step (torchreid/optim/radam.py:51-130, degenerated_to_sgd=True; built at
+ * torchreid/optim/optimizer.py:149-155) -- NOT torch.optim.RAdam: decoupled decay p -= wd*lr*p only where an update
+ * follows, the rectified branch from N_sma >= 5 with denominator sqrt(v)+eps, below it p -= lr*exp_avg/(1-beta1^t).
+ * N_sma and step_size are derived from `step` (1-based) in double on every call (radam.py:94-110; the reference's
+ * ten-slot buffer only caches them), so the call keeps no state.  step < 1, n < 0 or a NULL pointer: IEEE_ERR_BAD_ARG. */
+int ieee_radam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                    float beta2, float eps, float weight_decay, int64_t step, void* stream);
 
 /* ---- re-ranking ----------------------------------------------- */
 /* k-reciprocal re-ranking, torchreid/utils/rerank.py:31-113 (engine/engine.py:402-406): device matrices

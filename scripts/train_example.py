@@ -43,6 +43,12 @@ def main():
     ap.add_argument("--batch", type=int, default=16, help="GLOBAL train batch (identities x 4 instances)")
     ap.add_argument("--workers", type=int, default=4)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--optim", default="sgd", choices=["adam", "amsgrad", "sgd", "rmsprop", "radam"])
+    ap.add_argument("--staged-lr", action="store_true", help="the reference's fine-tuning recipe: the children named in "
+                    "--new-layers train at --lr, every other child at --lr * --base-lr-mult")
+    ap.add_argument("--new-layers", default="", help="comma-separated children of the model, e.g. "
+                    "fc_R,fc_N,fc_T,classifier_R,classifier_N,classifier_T")
+    ap.add_argument("--base-lr-mult", type=float, default=0.1)
     ap.add_argument("--eval-freq", type=int, default=-1)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
@@ -82,7 +88,8 @@ def main():
 
     model = build_model("ieee3modalPart", num_classes=dm.num_train_pids, loss="margin", pretrained=False, use_gpu=True,
                         compute_dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32)
-    optimizer = build_optimizer(model, optim="sgd", lr=args.lr, weight_decay=5e-4, momentum=0.9)
+    optimizer = build_optimizer(model, optim=args.optim, lr=args.lr, weight_decay=5e-4, momentum=0.9, staged_lr=args.staged_lr,
+                                new_layers=[n for n in args.new_layers.split(",") if n], base_lr_mult=args.base_lr_mult)
     scheduler = build_lr_scheduler(optimizer, "multi_step", stepsize=[max(1, args.epochs * 2 // 3)], gamma=0.1)
     ranks = [r for r in (1, 5, 10, 20) if r <= len(dataset.gallery)]     # (the reference raises IndexError on a gallery of < 20)
     engine = Image3MEngine(dm, model, optimizer, margin=1, weight_m=1, weight_x=1, scheduler=scheduler, use_gpu=True,
