@@ -359,11 +359,38 @@ class IEEE3modalPart(nn.Module):
                                                                  device=self._flat_counters.device)
         self._flat_counters += self._counter_inc
 
+    _TRUNK_OUT = "backbone.{m}.layer4.2.conv3.a"     # the executor's name of the three trunk outputs (one tensor)
+
+    def trunk_maps(self, imgs):
+        """The trunk outputs of the three modalities (resnet_R / _N / _T, ieee3modalPart.py:440-442) as the executor holds
+        them: one [3, B, H/16, W/16, 2048] channels-last tensor in the compute dtype, modality order [RGB, NI, TI].  Runs
+        one eval-mode forward and returns a VIEW of the executor's workspace -- no permute, no copy: it is valid until the
+        next forward of this model (which overwrites it); clone it to keep it.  Eval mode only."""
+        assert isinstance(imgs, (list, tuple)) and len(imgs) == 3, "expected [RGB, NI, TI]"
+        if self.training:
+            raise RuntimeError("feature maps are the eval-mode trunk outputs: call `model.eval()` first")
+        B, C, H, W = imgs[0].shape
+        assert C == 3
+        net = self.native_net(B, H, W)
+        with torch.no_grad():
+            net.forward(imgs, training=False)
+        t = net.tensor(self._TRUNK_OUT)
+        h, w = H, W
+        for _ in range(4):                       # stem conv, max-pool, layer2, layer3: each (n - 1) // 2 + 1; last_stride = 1
+            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        assert 3 * B * h * w * 2048 == t.numel(), "unexpected trunk output size"
+        return t.view(3, B, h, w, 2048)
+
     def forward(self, x, return_featuremaps=False):
         """x: list/tuple of three [B,3,H,W] tensors in the order [RGB, NI, TI].  The second positional
-        argument is accepted and ignored: the reference's engine passes `timeids` there
-        (engine/engine.py:366, 450-451)."""
+        argument is accepted and ignored unless it is the value True: the reference's engine passes `timeids`
+        there (engine/engine.py:366, 450-451).  `return_featuremaps=True` (eval mode) returns the three trunk
+        outputs [map_R, map_N, map_T], each a fresh fp32 NCHW tensor [B, 2048, H/16, W/16] -- what the
+        reference's tools/visualize_actmap.py:59-65 asks a model for; `trunk_maps` is the copy-free form."""
         assert isinstance(x, (list, tuple)) and len(x) == 3, "expected [RGB, NI, TI]"
+        if return_featuremaps is True:           # identity, not truthiness: a `timeids` tensor in this position is not a request
+            maps = self.trunk_maps(x)
+            return [maps[m].permute(0, 3, 1, 2).to(torch.float32).contiguous() for m in range(3)]
         B, C, H, W = x[0].shape
         assert C == 3
         net = self.native_net(B, H, W)

@@ -1,7 +1,11 @@
 """Ranked-result figures, the reference's torchreid/utils/reidtools.py::visualize_ranked_results (:18-154) with the
 same call, layout and printed progress.  The ranking comes from the device (ieee_amd.metrics.rank_topk: k indices per
 query, the same-identity same-camera entries already skipped) instead of a host argsort of the whole matrix (:49);
-the figures are drawn with PIL."""
+the figures are drawn with PIL.
+
+Activation-map figures, the reference's tools/visualize_actmap.py::visactmap (:25-154) with the same call, file layout
+and printed progress.  The channel energy of the trunk output and the three-panel figures are computed on the device
+(ieee_actmap_energy / ieee_actmap_render); the finished bytes cross to the host once per batch and PIL writes them."""
 from __future__ import absolute_import, print_function
 
 import os
@@ -9,7 +13,7 @@ import os.path as osp
 
 import numpy as np
 
-__all__ = ['visualize_ranked_results']
+__all__ = ['visualize_ranked_results', 'jet_table', 'activation_maps', 'render_actmaps', 'visactmap']
 
 GRID_SPACING = 10
 QUERY_EXTRA_SPACING = 90
@@ -81,3 +85,187 @@ def visualize_ranked_results(distmat, dataset, data_type='image', width=128, hei
 
     print('Done. Images have been saved to "{}" ...'.format(save_dir))
     return ranked
+
+
+# ---- activation maps (tools/visualize_actmap.py) ---------------------------------------------------------------------
+IMAGENET_MEAN = [0.485, 0.456, 0.406]
+IMAGENET_STD = [0.229, 0.224, 0.225]
+_MODALS = ('RGB', 'NI', 'TI')
+_lut_cache = {}
+
+
+def jet_table():
+    """The default colour table of the activation-map figures: the closed-form jet, uint8 [256][3] RGB.  With v = i / 255:
+    r = clip(min(4v - 1.5, -4v + 4.5), 0, 1), g = clip(min(4v - 0.5, -4v + 3.5), 0, 1), b = clip(min(4v + 0.5,
+    -4v + 2.5), 0, 1), bytes floor(255 c + 0.5), in float64.  (The reference calls cv2.applyColorMap(am, COLORMAP_JET),
+    visualize_actmap.py:131; whoever has cv2 can hand its table -- RGB order -- to render_actmaps / visactmap instead.)"""
+    v = np.arange(256, dtype=np.float64) / 255.0
+    tab = np.empty((256, 3), dtype=np.uint8)
+    for c, (lo, hi) in enumerate(((-1.5, 4.5), (-0.5, 3.5), (0.5, 2.5))):
+        tab[:, c] = np.floor(255.0 * np.clip(np.minimum(4.0 * v + lo, -4.0 * v + hi), 0.0, 1.0) + 0.5).astype(np.uint8)
+    return tab
+
+
+def _energy(x):
+    """x: contiguous channels-last [..., h, w, C] on the device, fp32 or bf16 -> fp32 [..., h, w]"""
+    import torch
+    from . import _lib
+    lib = _lib.require_gpu()
+    lead, (h, w, C) = x.shape[:-3], x.shape[-3:]
+    n = 1
+    for d in lead:
+        n *= int(d)
+    out = torch.empty(tuple(lead) + (h, w), dtype=torch.float32, device=x.device)
+    dt = _lib.IEEE_BF16 if x.dtype == torch.bfloat16 else _lib.IEEE_F32
+    _lib.check(lib.ieee_actmap_energy(_lib.ptr(x), dt, n, h * w, C, _lib.ptr(out), _lib.stream()))
+    return out
+
+
+def activation_maps(featuremaps):
+    """Activation maps of convolutional feature maps (visualize_actmap.py:84-88): the channel energy sum_c x^2 of every
+    position, L2-normalised over each image's positions (F.normalize, eps 1e-12), on the device.
+
+    featuremaps: a 5-D tensor is the native channels-last form [M, B, h, w, C] (`model.trunk_maps`), read in place; a
+    4-D tensor is one NCHW map [B, C, h, w] as a torch model returns it (made channels-last with torch first); a list
+    or tuple of those gives one more leading axis.  fp32 and bf16 are read as they are, anything else as fp32.
+    Returns fp32 [..., h, w] on the device."""
+    import torch
+    if isinstance(featuremaps, (list, tuple)):
+        return torch.stack([activation_maps(f) for f in featuremaps])
+    x = featuremaps
+    if not torch.is_tensor(x) or x.dim() not in (4, 5):
+        raise ValueError('activation_maps: expected [B, C, h, w], the native [M, B, h, w, C], or a list of them; got %s'
+                         % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+    from . import _lib
+    _lib.require_gpu()
+    x = x.detach()
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.to(torch.float32)
+    x = x.cuda()
+    if x.dim() == 4:
+        x = x.permute(0, 2, 3, 1)
+    return _energy(x.contiguous())
+
+
+def _lut_on(device, colormap):
+    import torch
+    if colormap is None:
+        key = str(device)
+        if key not in _lut_cache:
+            _lut_cache[key] = torch.from_numpy(jet_table()).to(device)
+        return _lut_cache[key]
+    lut = torch.as_tensor(np.ascontiguousarray(colormap.cpu().numpy() if torch.is_tensor(colormap) else colormap))
+    if lut.dtype != torch.uint8 or lut.numel() != 768:
+        raise ValueError('colormap: expected 256 RGB triples of uint8')
+    return lut.reshape(256, 3).contiguous().to(device)
+
+
+def render_actmaps(imgs, amaps, width, height, img_mean=None, img_std=None, colormap=None, return_index=False):
+    """The figures of visualize_actmap.py:119-146 for a batch, on the device.
+
+    imgs: the normalised network input [N, 3, height, width] of the modality shown, or None (then only the colour
+    indices are computed); amaps: [N, h, w] from `activation_maps`; colormap: uint8 [256][3] RGB, default `jet_table()`.
+    Returns the uint8 grids [N, height, 3 * width + 20, 3] (RGB; left to right: image, coloured map, overlay, two 10-pixel
+    white gaps), or (grids, index) with return_index, index = the uint8 [N, height, width] colour index before the table;
+    grids is None when imgs is None.  The arithmetic is fixed by include/ieee_amd.h (ieee_actmap_render)."""
+    import ctypes
+    import torch
+    from . import _lib
+    lib = _lib.require_gpu()
+    if img_mean is None or img_std is None:
+        img_mean, img_std = IMAGENET_MEAN, IMAGENET_STD
+    amaps = amaps.detach().to(device='cuda', dtype=torch.float32).contiguous()
+    if amaps.dim() != 3:
+        raise ValueError('render_actmaps: amaps must be [N, h, w], got %s' % (tuple(amaps.shape),))
+    N, h, w = amaps.shape
+    dev = amaps.device
+    grids = index = None
+    if imgs is not None:
+        if tuple(imgs.shape) != (N, 3, height, width):
+            raise ValueError('render_actmaps: imgs must be [%d, 3, %d, %d] (N, 3, height, width), got %s'
+                             % (N, height, width, tuple(imgs.shape)))
+        imgs = imgs.detach().to(device=dev, dtype=torch.float32).contiguous()
+        grids = torch.empty((N, height, 3 * width + 2 * GRID_SPACING, 3), dtype=torch.uint8, device=dev)
+    elif not return_index:
+        raise ValueError('render_actmaps: without imgs there is only the index to return (return_index=True)')
+    if return_index:
+        index = torch.empty((N, height, width), dtype=torch.uint8, device=dev)
+    mean3 = (ctypes.c_float * 3)(*[float(v) for v in img_mean])
+    std3 = (ctypes.c_float * 3)(*[float(v) for v in img_std])
+    lut = _lut_on(dev, colormap)
+    _lib.check(lib.ieee_actmap_render(_lib.ptr(amaps), h, w, _lib.ptr(imgs), mean3, std3, _lib.ptr(lut), N, height, width,
+                                      _lib.ptr(grids), _lib.ptr(index), _lib.stream()))
+    return (grids, index) if return_index else grids
+
+
+def visactmap(model, test_loader, save_dir, save_name, width, height, use_gpu, modal, img_mean=None, img_std=None,
+              colormap=None):
+    """tools/visualize_actmap.py::visactmap (:25-154): for every query image of every target dataset, the figure [image |
+    activation map | overlay] of modality `modal` ('RGB', 'NI' or 'TI') into <save_dir>/actmap_vis_<save_name>/<basename
+    of the image>.jpg.  A model with `trunk_maps` (IEEE3modalPart) is read through it, without a copy of the maps; any
+    other model is called as the reference calls it, `model(imgs, return_featuremaps=True)`.  Batches may be on the CPU
+    or the device and are left as they were (the reference de-normalises the caller's tensors in place, :119-120); every
+    image must already have the figure's size (height, width), which the reference's slice assignment (:143) implies.
+    The kernels need the device: `use_gpu=False` is an error.  One device-to-host copy per batch.  Returns the paths
+    written."""
+    import torch
+    from PIL import Image
+    from .data.loader import DeviceLoader
+    if modal not in _MODALS:
+        print("Unknow modal!")
+        raise RuntimeError("visactmap: modal must be one of %s, got %r" % (list(_MODALS), modal))
+    mi = _MODALS.index(modal)
+    if img_mean is None or img_std is None:
+        # use imagenet mean and std
+        img_mean, img_std = IMAGENET_MEAN, IMAGENET_STD
+    if not use_gpu:
+        from ._lib import IeeeAmdError
+        raise IeeeAmdError("visactmap: the activation-map kernels run on the GPU; there is no CPU path (use_gpu=False)")
+
+    model.eval()
+    core = getattr(model, 'module', model)
+    native = hasattr(core, 'trunk_maps')
+    written = []
+    with torch.no_grad():
+        for target in list(test_loader.keys()):
+            data_loader = test_loader[target]['query']  # only process query images
+            actmap_dir = osp.join(save_dir, 'actmap_vis_' + save_name)
+            os.makedirs(actmap_dir, exist_ok=True)
+            print('Visualizing activation maps for {} ...'.format(target))
+            # the reference's collate gives impath as [modality][sample] (:98-102); this package's DeviceLoader keeps the
+            # records' own [sample][modality]
+            by_sample = isinstance(data_loader, DeviceLoader)
+
+            for batch_idx, data in enumerate(data_loader):
+                imgs, paths = data['img'], data['impath']
+                for i in range(len(imgs)):
+                    if tuple(imgs[i].shape[-2:]) != (height, width):
+                        raise ValueError('visactmap: images of %s are %d x %d but the figure is height %d x width %d; load '
+                                         'them at the size given here' % (_MODALS[i] if i < 3 else i, imgs[i].shape[-2],
+                                                                          imgs[i].shape[-1], height, width))
+                dev_imgs = [im.cuda() for im in imgs]         # new list: the caller's stays as it is
+                if native:
+                    amaps = activation_maps(core.trunk_maps(dev_imgs)[mi:mi + 1])[0]
+                else:
+                    try:
+                        outputs = model(dev_imgs, return_featuremaps=True)[mi]
+                    except TypeError:
+                        raise TypeError('forward() got unexpected keyword argument "return_featuremaps". '
+                                        'Please add return_featuremaps as an input argument to forward(). When '
+                                        'return_featuremaps=True, return feature maps only.')
+                    if outputs.dim() != 4:
+                        raise ValueError('The model output is supposed to have shape of (b, c, h, w), i.e. 4 dimensions, '
+                                         'but got {} dimensions. Please make sure you set the model output at eval mode '
+                                         'to be the last convolutional feature maps'.format(outputs.dim()))
+                    amaps = activation_maps(outputs)
+                grids = render_actmaps(dev_imgs[mi], amaps, width, height, img_mean, img_std, colormap).cpu().numpy()
+                for j in range(grids.shape[0]):
+                    path = paths[j][mi] if by_sample else paths[mi][j]
+                    imname = osp.basename(osp.splitext(path)[0])
+                    out = osp.join(actmap_dir, imname + '.jpg')
+                    Image.fromarray(grids[j]).save(out, quality=95)       # cv2.imwrite's default
+                    written.append(out)
+
+                if (batch_idx + 1) % 10 == 0:
+                    print('- done batch {}/{}'.format(batch_idx + 1, len(data_loader)))
+    return written

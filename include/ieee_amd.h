@@ -106,6 +106,34 @@ int ieee_rank_topk(const float* distmat, int64_t ldd, int64_t num_q, int64_t num
                    const int32_t* g_camids, int exclude_same_cam, int64_t k, int32_t* out_idx,
                    float* out_dist, void* stream);
 
+/* ---- activation maps (tools/visualize_actmap.py) --------------------------- */
+/* tools/visualize_actmap.py:84-88: outputs = (outputs**2).sum(1); F.normalize(outputs.view(b, h*w), p=2, dim=1).
+ * x [N][P][C], NHWC (P = h*w positions, C channels innermost), IEEE_F32 or IEEE_BF16, 16-byte aligned; out fp32 [N][P]:
+ *   E[n][p] = sum_c x[n][p][c]^2 in fp32,   out[n][p] = E[n][p] / max(||E[n][:]||_2, 1e-12)
+ * (F.normalize's eps: an all-zero map gives zeros, not NaN).  One workgroup per image; the order of every sum is fixed
+ * (lane, shuffle butterfly, LDS in wave order) and there are no atomics, so two calls give the same bits.
+ * C % 8 == 0 and 1 <= P <= 4096, else IEEE_ERR_BAD_ARG before any launch.  No workspace, no host sync. */
+int ieee_actmap_energy(const void* x, int dtype, int64_t N, int64_t P, int64_t C, float* out, void* stream);
+/* tools/visualize_actmap.py:119-146: the three-panel figure of every image of a batch, finished bytes only.
+ * amap fp32 [N][h][w] (h*w <= 4096).  img: the normalised network input, fp32 NCHW [N][3][height][width], or NULL -- then
+ * only index_out is written.  mean3 / std3: HOST pointers to three floats (read during the call; :119-120).  lut: uint8
+ * [256][3] RGB colour table on the device (:131 uses COLORMAP_JET).  grid_out uint8 [N][height][3*width + 20][3] RGB, left
+ * to right the de-normalised image, the coloured map, the overlay, with two 10-pixel white gaps (:138-146; the reference
+ * builds the figure in BGR for cv2.imwrite and adds the RGB image to the BGR map in its overlay, :134 -- here the overlay
+ * adds like channels).  index_out uint8 [N][height][width]: the colour index before the table, or NULL.  Arithmetic,
+ * fp32 without fused multiply-adds unless stated:
+ *   resize (:126, cv2.resize INTER_LINEAR positions): sx = (dx + 0.5) * (w / width) - 0.5, x0 = floor(sx), fx = sx - x0;
+ *     x0 < 0 -> x0 = 0, fx = 0; x0 >= w - 1 -> x0 = w - 1, fx = 0; x1 = min(x0 + 1, w - 1); the same in y; rows y0 and y1
+ *     are interpolated horizontally, then the two results vertically, each step a + (b - a) * f
+ *   index (:127-130): floor(255 * (v - min) / ((max - min) + 1e-12f)), min / max over the RESIZED map of the image
+ *   image (:119-121): c = clamp(x * std + mean, 0, 1), byte = floor(c * 255)
+ *   overlay (:134-136): trunc(min(0.3 * image + 0.7 * colour, 255)) in double
+ * One workgroup per image, two passes over the figure (min / max, then the bytes); width <= 2048 (a figure row is
+ * assembled on chip), else IEEE_ERR_BAD_ARG before any launch.  No workspace, no host sync. */
+int ieee_actmap_render(const float* amap, int64_t h, int64_t w, const float* img, const float* mean3, const float* std3,
+                       const uint8_t* lut, int64_t N, int64_t height, int64_t width, uint8_t* grid_out,
+                       uint8_t* index_out, void* stream);
+
 /* ---- convolution as implicit GEMM over NHWC (MFMA) ------------------------ */
 /* These replace torch's conv2d forward / backward as dispatched by the
  * reference's Bottleneck.forward (torchreid/models/resnet.py:164-184), the
