@@ -123,19 +123,21 @@ class Engine(object):
     def run(self, save_dir='log', max_epoch=0, start_epoch=0, print_freq=10, fixbase_epoch=0, open_layers=None,
             start_eval=0, eval_freq=-1, test_only=False, dist_metric='euclidean', normalize_feature=False,
             visrank=False, visrank_topk=10, use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False,
-            rerank_k1=26, rerank_k2=7):
+            rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None):
         """engine.py:126-232.  As in the reference there is NO evaluation or checkpoint after the last epoch (the
         `(epoch + 1) != max_epoch` guard, :216), and re-ranking applies to test_only runs (its docstring, :171-172;
         the in-loop test call does not pass it on, :217-225).  rerank: False, True (k-reciprocal) or 'gnn' (see test;
-        rerank_k1 / rerank_k2 belong to 'gnn' alone)."""
+        rerank_k1 / rerank_k2 belong to 'gnn' alone).  vistsne / vistsne_labels: see test."""
         if visrank and not test_only:
             raise ValueError('visrank can be set to True only if test_only=True')
+        if vistsne and not test_only:
+            raise ValueError('vistsne can be set to True only if test_only=True')
         _check_rerank(rerank)
         eval_args = dict(dist_metric=dist_metric, normalize_feature=normalize_feature, save_dir=save_dir,
                          use_metric_cuhk03=use_metric_cuhk03, ranks=ranks)
         if test_only:
             self.test(rerank=rerank, rerank_k1=rerank_k1, rerank_k2=rerank_k2, visrank=visrank,
-                      visrank_topk=visrank_topk, **eval_args)
+                      visrank_topk=visrank_topk, vistsne=vistsne, vistsne_labels=vistsne_labels, **eval_args)
             return
         began = time.time()
         self.start_epoch, self.max_epoch = start_epoch, max_epoch
@@ -220,13 +222,18 @@ class Engine(object):
 
     # ---- evaluation ----------------------------------------------------------------------------------------------
     def test(self, dist_metric='euclidean', normalize_feature=False, visrank=False, visrank_topk=10, save_dir='',
-             use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7):
+             use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7, vistsne=False,
+             vistsne_labels=None):
         """every target dataset in turn (engine.py:287-337); returns the last one's mAP like the reference.
         rerank: False; True = k-reciprocal re-ranking (engine.py:402-406); 'gnn' = GNN re-ranking
         (ieee_amd.rerank.gnn_distmat with rerank_k1, rerank_k2, which the k-reciprocal branch ignores).  The GNN step is
         always handed L2-normalised descriptors, F.normalize(., p=2, dim=1), whatever dist_metric and normalize_feature
         say: the method ranks by the raw inner product and the reference's driver feeds it normalised rows.  Any other
-        string raises ValueError; other values keep their truthiness."""
+        string raises ValueError; other values keep their truthiness.
+        vistsne: after each report, the feature-space figure that the reference's evaluator draws under its visrank flag
+        (engine.py:437-439, 463-490): t-SNE of the three 768-wide slices of the query descriptors into
+        <save_dir>/vistsne_<name>/<labels>.jpg (ieee_amd.reidtools.show_points_multimodal).  vistsne_labels: the
+        relabelled identities to draw; None draws random.sample(range(1, 30), 6) like the reference."""
         _check_rerank(rerank)
         self.set_model_mode('eval')
         mAP = 0.0
@@ -238,7 +245,8 @@ class Engine(object):
                                         normalize_feature=normalize_feature, visrank=visrank,
                                         visrank_topk=visrank_topk, save_dir=save_dir,
                                         use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, rerank=rerank,
-                                        rerank_k1=rerank_k1, rerank_k2=rerank_k2)
+                                        rerank_k1=rerank_k1, rerank_k2=rerank_k2, vistsne=vistsne,
+                                        vistsne_labels=vistsne_labels)
             if self.writer is not None:
                 self.writer.add_scalar('Test/{}/rank1'.format(name), rank1, self.epoch)
                 self.writer.add_scalar('Test/{}/mAP'.format(name), mAP, self.epoch)
@@ -286,7 +294,7 @@ class Engine(object):
     @torch.no_grad()
     def _evaluate(self, dataset_name='', query_loader=None, gallery_loader=None, dist_metric='euclidean',
                   normalize_feature=False, visrank=False, visrank_topk=10, save_dir='', use_metric_cuhk03=False,
-                  ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7):
+                  ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None):
         """descriptors -> distance matrix -> CMC / mAP, printed like engine.py:339-441; returns (rank-1, mAP)"""
         _check_rerank(rerank)
         if visrank and ddp.world_size() > 1:
@@ -294,6 +302,10 @@ class Engine(object):
                                'forms: run engine.run(test_only=True, visrank=True) in one process on one GPU '
                                '(a plain `python` command with WORLD_SIZE unset or 1, not torchrun or '
                                'ieee_amd.dist.launch)'.format(ddp.world_size()))
+        if vistsne and ddp.world_size() > 1:
+            raise RuntimeError('vistsne draws one figure from the whole query set: run engine.run(test_only=True, '
+                               'vistsne=True) in one process on one GPU (a plain `python` command with WORLD_SIZE unset '
+                               'or 1, not torchrun or ieee_amd.dist.launch), not over {} ranks'.format(ddp.world_size()))
         clock = AverageMeter()
         say = print if ddp.rank() == 0 else (lambda *a, **k: None)     # one report, not one per rank
         if ddp.world_size() > 1 and self.model is not None and hasattr(self.model, "_flat_buffers"):
@@ -334,6 +346,11 @@ class Engine(object):
         say('\n')
         if visrank:     # engine.py:423-431 (commented out there): the ranked figures, from the matrix ranked above
             self._visrank(distmat, dataset_name, query_loader, gallery_loader, visrank_topk, save_dir)
+        if vistsne:     # engine.py:437-439: what the reference's visrank flag draws
+            import random
+            from .reidtools import show_points_multimodal
+            labels = list(vistsne_labels) if vistsne_labels is not None else random.sample(range(1, 30), 6)
+            show_points_multimodal(qf, q_pids, labels, osp.join(save_dir, 'vistsne_' + dataset_name))
         return cmc[0], mAP
 
     def _test_records(self, name, query_loader, gallery_loader):

@@ -5,7 +5,11 @@ the figures are drawn with PIL.
 
 Activation-map figures, the reference's tools/visualize_actmap.py::visactmap (:25-154) with the same call, file layout
 and printed progress.  The channel energy of the trunk output and the three-panel figures are computed on the device
-(ieee_actmap_energy / ieee_actmap_render); the finished bytes cross to the host once per batch and PIL writes them."""
+(ieee_actmap_energy / ieee_actmap_render); the finished bytes cross to the host once per batch and PIL writes them.
+
+Feature-space figures, the reference's torchreid/engine/engine.py::showPointMultiModal (:453-490): one exact t-SNE per
+768-wide descriptor slice, all three as one batch on the device (ieee_tsne_affinities / ieee_tsne_run) where the
+reference calls sklearn.manifold.TSNE three times, and one scatter drawn with PIL where it calls matplotlib."""
 from __future__ import absolute_import, print_function
 
 import os
@@ -13,7 +17,8 @@ import os.path as osp
 
 import numpy as np
 
-__all__ = ['visualize_ranked_results', 'jet_table', 'activation_maps', 'render_actmaps', 'visactmap']
+__all__ = ['visualize_ranked_results', 'jet_table', 'activation_maps', 'render_actmaps', 'visactmap', 'tsne_embed',
+           'relabel', 'draw_points', 'show_points_multimodal']
 
 GRID_SPACING = 10
 QUERY_EXTRA_SPACING = 90
@@ -269,3 +274,184 @@ def visactmap(model, test_loader, save_dir, save_name, width, height, use_gpu, m
                 if (batch_idx + 1) % 10 == 0:
                     print('- done batch {}/{}'.format(batch_idx + 1, len(data_loader)))
     return written
+
+
+# ---- descriptor t-SNE (torchreid/engine/engine.py:453-490) -------------------------------------------------------------
+# darkorange, limegreen, royalblue, red, darkviolet, black (engine.py:474)
+TSNE_COLORS = ((255, 140, 0), (50, 205, 50), (65, 105, 225), (255, 0, 0), (148, 0, 211), (0, 0, 0))
+TSNE_ALPHA = 0.4
+_FIGURE_MARGIN = 0.1      # the unit square of the coordinates sits inside this share of the canvas on every side
+
+
+def _pca_init(x):
+    """sklearn's init='pca' for x [B, N, d] on the device: the top two principal axes from the eigenvectors of the centred
+    covariance in float64, each signed so that its largest-magnitude loading is positive, the projection scaled so that the
+    first column has standard deviation 1e-4 (sklearn/manifold/_t_sne.py, _fit)"""
+    import torch
+    xc = x.to(torch.float64)
+    xc = xc - xc.mean(1, keepdim=True)
+    _, vecs = torch.linalg.eigh(xc.transpose(1, 2) @ xc)                 # ascending eigenvalues
+    v = vecs[:, :, -2:].flip(2)                                          # [B, d, 2], the largest first
+    lead = torch.gather(v, 1, v.abs().argmax(1, keepdim=True))           # [B, 1, 2]
+    v = v * torch.where(lead < 0, -torch.ones_like(lead), torch.ones_like(lead))
+    y = xc @ v
+    return (y / y[:, :, :1].std(1, unbiased=False, keepdim=True) * 1e-4).to(torch.float32)
+
+
+def tsne_embed(features, perplexity=30.0, n_iter=1000, early_exaggeration=12.0, exaggeration_iters=250,
+               learning_rate='auto', init='pca', generator=None, return_info=False):
+    """Exact t-SNE of descriptors into the plane, on the device: what sklearn.manifold.TSNE(n_components=2,
+    method='exact') computes, with sklearn's perplexity search, exaggeration, momentum and gains schedule
+    (include/ieee_amd.h: ieee_tsne_affinities, ieee_tsne_run).  All n_iter iterations always run: sklearn's two
+    early-stopping rules (min_grad_norm, n_iter_without_progress) would need a host read every 50 iterations.
+
+    features: [N, d], or [B, N, d] for B independent problems in one batch (N <= 12288).  Distances come from
+    compute_distance_matrix(x, x).  learning_rate 'auto' = max(N / early_exaggeration / 4, 50).  init: an [N, 2] /
+    [B, N, 2] tensor used as given, 'random' (1e-4 * randn from `generator`, a torch.Generator of the device), or 'pca'.
+    Returns fp32 [N, 2] / [B, N, 2] on the device of `features` (CPU in, CPU out); with return_info also a dict:
+    kl_history and grad_norm_history [B, n_iter] (the KL divergence at each iteration's coordinates before its update,
+    the gradient's 2-norm), beta [B, N], kl_divergence [B] (the last history value; without the leading B for [N, d])."""
+    import torch
+    from . import _lib
+    from .metrics.distance import compute_distance_matrix
+    if not torch.is_tensor(features) or features.dim() not in (2, 3):
+        raise ValueError('tsne_embed: features must be a [N, d] or [B, N, d] tensor, got %s'
+                         % (tuple(features.shape) if torch.is_tensor(features) else type(features).__name__))
+    single = features.dim() == 2
+    B, N, d = (1,) + tuple(features.shape) if single else tuple(features.shape)
+    if perplexity >= N:
+        raise ValueError('perplexity must be less than n_samples')
+    lib = _lib.require_gpu()
+    home = features.device
+    x = features.detach().to(device='cuda', dtype=torch.float32).reshape(B, N, d).contiguous()
+    dev = x.device
+    if learning_rate == 'auto':
+        learning_rate = max(N / early_exaggeration / 4.0, 50.0)
+    if torch.is_tensor(init):
+        if tuple(init.shape) != ((N, 2) if single else (B, N, 2)):
+            raise ValueError('tsne_embed: init must be %s, got %s' % ((N, 2) if single else (B, N, 2), tuple(init.shape)))
+        Y = init.detach().to(device=dev, dtype=torch.float32).reshape(B, N, 2).clone().contiguous()
+    elif init == 'random':
+        Y = 1e-4 * torch.randn((B, N, 2), dtype=torch.float32, device=dev, generator=generator)
+    elif init == 'pca':
+        Y = _pca_init(x).contiguous()
+    else:
+        raise ValueError("tsne_embed: init must be 'pca', 'random' or a tensor, got %r" % (init,))
+
+    ldp = (N + 3) // 4 * 4
+    dist = torch.stack([compute_distance_matrix(x[b], x[b]) for b in range(B)])
+    P = torch.empty((B, N, ldp), dtype=torch.float32, device=dev)
+    beta = torch.empty((B, N), dtype=torch.float32, device=dev)
+    nbytes = lib.ieee_tsne_workspace_bytes(N, B)
+    if nbytes < 0:
+        _lib.check(-1)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.ieee_tsne_affinities(_lib.ptr(dist), N, N, B, float(perplexity), _lib.ptr(P), ldp, _lib.ptr(beta),
+                                        _lib.ptr(work), nbytes, _lib.stream()))
+    update, gains = torch.zeros_like(Y), torch.ones_like(Y)
+    history = torch.empty((B, n_iter, 2), dtype=torch.float32, device=dev) if return_info else None
+    _lib.check(lib.ieee_tsne_run(_lib.ptr(P), ldp, N, B, _lib.ptr(Y), _lib.ptr(update), _lib.ptr(gains), 0, int(n_iter),
+                                 int(exaggeration_iters), float(early_exaggeration), float(learning_rate),
+                                 _lib.ptr(history), _lib.ptr(work), nbytes, _lib.stream()))
+    out = (Y[0] if single else Y).to(home)
+    if not return_info:
+        return out
+    pick = (lambda t: t[0]) if single else (lambda t: t)
+    info = {'kl_history': pick(history[:, :, 0]).to(home), 'grad_norm_history': pick(history[:, :, 1]).to(home),
+            'beta': pick(beta).to(home),
+            'kl_divergence': pick(history[:, -1, 0]).to(home) if n_iter > 0 else None}
+    return out, info
+
+
+def relabel(labels):
+    """engine.py:453-461: a consecutive index that moves on wherever the label changes from one row to the next"""
+    out, index = [], 0
+    for i, v in enumerate(labels):
+        if i > 0 and v != labels[i - 1]:
+            index += 1
+        out.append(index)
+    return out
+
+
+def _marker(kind, cx, cy, r):
+    """polygon of a star or an upward triangle around (cx, cy); None for the circle"""
+    import math
+    if kind == 1:
+        return None
+    if kind == 2:
+        return [(cx + r * math.sin(a), cy - r * math.cos(a)) for a in (0.0, 2.0 * math.pi / 3.0, 4.0 * math.pi / 3.0)]
+    pts = []
+    for k in range(10):
+        a, rad = k * math.pi / 5.0, (r if k % 2 == 0 else 0.382 * r)
+        pts.append((cx + rad * math.sin(a), cy - rad * math.cos(a)))
+    return pts
+
+
+def draw_points(coords, labels, draw_label, save_path, size=2000):
+    """The scatter of engine.py:482-490 with PIL: coords [3, N, 2] in [0, 1] (one slice per marker: star, circle,
+    triangle), labels the relabelled identity of every row; only rows whose label is in draw_label are drawn, in colour
+    TSNE_COLORS[draw_label.index(label) % 6] at alpha 0.4, onto a white size x size canvas saved as JPEG.  x runs right
+    and y up, inside a margin of a tenth of the canvas; marker diameters follow matplotlib's s = 300, 300, 400 points^2
+    on a 20-inch figure.  No axes are drawn and no pixel equality with matplotlib is claimed."""
+    from PIL import Image, ImageDraw
+    coords = np.asarray(coords.detach().cpu().numpy() if hasattr(coords, 'detach') else coords, dtype=np.float64)
+    if coords.ndim != 3 or coords.shape[0] != 3 or coords.shape[2] != 2 or coords.shape[1] != len(labels):
+        raise ValueError('draw_points: coords must be [3, %d, 2], got %s' % (len(labels), coords.shape))
+    draw_label = list(draw_label)
+    canvas = Image.new('RGB', (size, size), (255, 255, 255))
+    span = size * (1.0 - 2.0 * _FIGURE_MARGIN)
+    radius = [0.5 * (s ** 0.5) * size / 1440.0 for s in (300.0, 300.0, 400.0)]      # points -> pixels: size / (20 * 72)
+    radius[0] *= 1.3                                                                # a star's tips reach past the circle
+    alpha = int(round(255 * TSNE_ALPHA))
+    for i, lab in enumerate(labels):
+        if lab not in draw_label:
+            continue
+        color = TSNE_COLORS[draw_label.index(lab) % 6]
+        for m in range(3):
+            r = radius[m]
+            cx = size * _FIGURE_MARGIN + coords[m, i, 0] * span
+            cy = size * (1.0 - _FIGURE_MARGIN) - coords[m, i, 1] * span
+            x0, y0 = int(cx - r) - 2, int(cy - r) - 2
+            box = (max(x0, 0), max(y0, 0), min(x0 + int(2 * r) + 5, size), min(y0 + int(2 * r) + 5, size))
+            if box[0] >= box[2] or box[1] >= box[3]:
+                continue
+            patch = canvas.crop(box).convert('RGBA')
+            layer = Image.new('RGBA', patch.size, (0, 0, 0, 0))
+            pen = ImageDraw.Draw(layer)
+            poly = _marker(m, cx - box[0], cy - box[1], r)
+            if poly is None:
+                pen.ellipse((cx - box[0] - r, cy - box[1] - r, cx - box[0] + r, cy - box[1] + r), fill=color + (alpha,))
+            else:
+                pen.polygon(poly, fill=color + (alpha,))
+            canvas.paste(Image.alpha_composite(patch, layer).convert('RGB'), box[:2])
+    os.makedirs(osp.dirname(save_path) or '.', exist_ok=True)
+    canvas.save(save_path, 'JPEG', quality=95)
+    return save_path
+
+
+def modality_slices(features):
+    """engine.py:467-469: columns 0:768, 768:1536, 1536:2304, by position -> [3, N, 768]"""
+    import torch
+    if features.dim() != 2 or features.shape[1] < 2304:
+        raise ValueError('expected [N, 2304] descriptors, got %s' % (tuple(features.shape),))
+    return torch.stack([features[:, 0:768], features[:, 768:1536], features[:, 1536:2304]])
+
+
+def minmax_scale(coords):
+    """engine.py:476-481: (y - min) / (max - min) per slice and axis, [..., N, 2] -> the same shape in [0, 1]"""
+    lo = coords.min(-2, keepdim=True).values
+    hi = coords.max(-2, keepdim=True).values
+    return (coords - lo) / (hi - lo)
+
+
+def show_points_multimodal(features, real_label, draw_label, save_path, **tsne_kwargs):
+    """engine.py::showPointMultiModal (:463-490): t-SNE of the three 768-wide slices of `features` [N, 2304] (one batched
+    tsne_embed call; tsne_kwargs go to it), min-max scaled per slice and axis, the rows whose relabelled identity is in
+    draw_label drawn into <save_path>/<str(draw_label)>.jpg.  Returns (path, scaled coordinates [3, N, 2])."""
+    draw_label = list(draw_label)
+    path = osp.join(save_path, str(draw_label) + '.jpg')
+    print('Draw points of features to {}'.format(path))
+    labels = relabel([int(v) for v in np.asarray(real_label).reshape(-1)])
+    coords = minmax_scale(tsne_embed(modality_slices(features), **tsne_kwargs))
+    draw_points(coords, labels, draw_label, path)
+    return path, coords

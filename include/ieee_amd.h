@@ -624,6 +624,46 @@ int ieee_gnn_rerank(const float* xq, const float* xg, int64_t Q, int64_t G, int6
  * rows fed the final product (M1, the unnormalised second round; M0 = the binary B when k2 = 1)}. */
 int ieee_gnn_rerank_layout(int64_t Q, int64_t G, int64_t d, int64_t k1, int64_t k2, int precision, int64_t* fields);
 
+/* ---- descriptor t-SNE (torchreid/engine/engine.py:463-490, showPointMultiModal) ---------------------------------- */
+/* Exact (dense, O(n^2)) t-SNE in 2 output dimensions, Student-t degree of freedom 1, what the reference gets from
+ * sklearn.manifold.TSNE(n_components=2).  `batch` independent problems of the same n run per call, on a grid axis (the
+ * three modalities are batch = 3).  Caller-owned memory, everything on `stream`, no host sync, no atomics, no graph
+ * capture; every sum has a fixed order, so two calls give the same bits.  Bounds, checked before anything is launched
+ * (IEEE_ERR_BAD_ARG, the error text names the function): 4 <= n <= 12288 (a distance row stays in LDS during the
+ * search; P for batch = 3 is then 1.7 GiB and the workspace 21 MiB: under 2 GiB together), 1 <= batch <= 65535,
+ * 0 < perplexity < n, ldd >= n, ldp >= n with ldp % 4 == 0 and P 16-byte aligned, Y 8-byte aligned, work_bytes >=
+ * ieee_tsne_workspace_bytes(n, batch) (-1 and the error text for n or batch out of range; one size serves both calls). */
+int64_t ieee_tsne_workspace_bytes(int64_t n, int64_t batch);
+/* dist [batch][n][ldd] fp32 squared Euclidean distances (what ieee_sqeuclid_distmat(x, x) writes; tiny negatives are
+ * fine) -> the joint matrix P [batch][n][ldp] fp32 and beta [batch][n] fp32.  Per row i, with d'_j = dist[i][j] -
+ * min_{k != i} dist[i][k] (the shift changes neither the row nor its entropy and keeps exp from underflowing on
+ * distances of 1e3..1e5; the diagonal takes no part): sklearn's _binary_search_perplexity -- beta = 1; H = log S +
+ * beta sum_j d'_j e_j / S with e_j = exp(-beta d'_j), S = sum_j e_j; done when |H - log(perplexity)| <= 1e-5 or after
+ * 100 steps; else beta moves to the middle of its bracket, doubling or halving while that side has no bound yet.
+ * beta d'_j is formed in double and rounded once; sums are fp32.  p_{j|i} = e_j / S for the beta returned, and
+ * P_ij = (p_{j|i} + p_{i|j}) / (2n): bitwise symmetric, diagonal 0, columns n..ldp-1 zero. */
+int ieee_tsne_affinities(const float* dist, int64_t ldd, int64_t n, int64_t batch, double perplexity, float* P,
+                         int64_t ldp, float* beta, void* work, int64_t work_bytes, void* stream);
+/* Iterations iter0 .. iter0 + n_iter - 1 of sklearn's _gradient_descent schedule, all enqueued by the one call (two
+ * launches each).  Y, update, gains [batch][n][2] fp32 are read and written, so a run can be resumed or stepped (start
+ * with update = 0, gains = 1).  Per iteration, with w_ij = 1 / (1 + |y_i - y_j|^2) for i != j and Z = sum_{i != j} w_ij:
+ *   g_i = 4 (alpha sum_j P_ij w_ij (y_i - y_j) - (sum_j w_ij^2 (y_i - y_j)) / Z)
+ *   gains += 0.2 where update * g < 0, else gains *= 0.8; gains = max(gains, 0.01)
+ *   update = momentum * update - learning_rate * (gains * g);  Y += update
+ * alpha = early_exaggeration and momentum = 0.5 for iterations below exaggeration_iters, then 1 and 0.8.
+ * history [batch][n_iter][2] or NULL: (KL = sum P log P + sum P log(1 + |y_i - y_j|^2) + (sum P) log Z of the plain P
+ * at the iteration's Y before the update, zero entries of P contributing 0; the 2-norm of g).  There is NO early
+ * stopping: sklearn's min_grad_norm and n_iter_without_progress checks would need a host read every 50 iterations. */
+int ieee_tsne_run(const float* P, int64_t ldp, int64_t n, int64_t batch, float* Y, float* update, float* gains,
+                  int64_t iter0, int64_t n_iter, int64_t exaggeration_iters, double early_exaggeration,
+                  double learning_rate, float* history, void* work, int64_t work_bytes, void* stream);
+/* Where ieee_tsne_run leaves its sums, for inspection after a call: fields[6] = {slabs (512 columns each), byte offset
+ * of the slab partials [batch][slabs][6][n] fp32, byte offset of the per-row sums [batch][6][n] fp32 of the LAST
+ * iteration (sum_j P w dx, sum_j P w dy, sum_j w^2 dx, sum_j w^2 dy, sum_j w, sum_j P log(1 + d^2); the last one only with a
+ * history), byte offset of [batch][2][n] fp32 (sum_j P log P, sum_j P; only with a history), byte offset of
+ * [batch][8] fp32 {Z, sum P log(1 + d^2), sum P log P, sum P, |g|^2, -, -, -}, 6}. */
+int ieee_tsne_layout(int64_t n, int64_t batch, int64_t* fields);
+
 /* ---- input pipeline ------------------------------------------ */
 /* The reference's per-image chain Resize((Ho,Wo)) -> RandomHorizontalFlip -> ToTensor -> Normalize
  * (torchreid/data/transforms.py:233-326; dataset.py:335-351) for N decoded uint8 images of ONE source size:
