@@ -51,3 +51,11 @@ def _decide_hw_queues():
 HW_QUEUES = _decide_hw_queues()
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # FeatureExtractor lives behind torch; `import ieee_amd` itself stays free of it (it runs before the HIP runtime starts)
+    if name == "FeatureExtractor":
+        from .feature_extractor import FeatureExtractor
+        return FeatureExtractor
+    raise AttributeError("module 'ieee_amd' has no attribute %r" % name)

@@ -8,6 +8,9 @@
 // Byte/integer work bound by HBM: nothing here belongs on the matrix cores.
 #include "common.h"
 
+#include <algorithm>
+#include <cmath>
+
 namespace ieee {
 
 constexpr int PRECISION_BITS = 32 - 8 - 2;
@@ -270,6 +273,144 @@ __global__ __launch_bounds__(256) void augment_final_kernel(const uint8_t* __res
   o[2 * plane] = f2;
 }
 
+// ---- ragged batch (ieee_resize_normalize_ragged): N images, each with its own (Hs, Ws), in ONE launch and with no host
+// tables.  A workgroup owns (image, band of R output rows): it computes Pillow's coefficients of every output column and of
+// its own output rows (axis_row below), runs the horizontal pass over the source rows its band reads into LDS (one packed
+// RGBx word per pixel, rounded to 8 bits like the uint8 intermediate of the two-launch form), then the vertical pass, the
+// flip and the normalisation out of LDS.  A band whose source rows exceed the LDS rows of the launch is done in groups of
+// output rows.  An axis that keeps its size gets the weight rows {1 << 22, 0}: the pass returns its input.
+
+// Pillow's precompute_coeffs + normalize_coeffs_8bpc (bilinear) for output index xx of one axis, as _axis_tables
+// (ieee_amd/data/transforms.py) restates them: fp64, the scale from the float32 of the size, ww summed left to right,
+// weights trunc(+-0.5 + k * 2^22).  Every product feeds a sum here: contraction into an fma would change the bits, so it is
+// off for this function.  bnd = (first source index, count <= cap); k[0 .. count) = weights; zero_to > count: k is zero-filled
+// up to there (the table form).
+__host__ __device__ inline int axis_ksize(int in_size, int out_size) {
+  const double scale = (double)((float)in_size - 0.0f) / (double)out_size;
+  const double support = scale > 1.0 ? scale : 1.0;
+  return (int)ceil(support) * 2 + 1;
+}
+
+__device__ __forceinline__ void axis_row(int in_size, int out_size, int xx, int cap, int zero_to, int* __restrict__ bnd,
+                                         int* __restrict__ k) {
+#pragma clang fp contract(off)
+  const double scale = (double)((float)in_size - 0.0f) / (double)out_size;
+  const double filterscale = scale > 1.0 ? scale : 1.0;
+  const double support = 1.0 * filterscale;
+  const double inv = 1.0 / filterscale;
+  const double center = ((double)xx + 0.5) * scale;
+  int xmin = (int)(center - support + 0.5);
+  if (xmin < 0) xmin = 0;
+  int xmax = (int)(center + support + 0.5);
+  if (xmax > in_size) xmax = in_size;
+  xmax -= xmin;
+  if (xmax > cap) xmax = cap;            // never taken: xmax <= ksize <= cap (the host checked); keeps the writes inside k
+  if (xmax < 0) xmax = 0;
+  double ww = 0.0;
+  for (int x = 0; x < xmax; ++x) {
+    double w = fabs(((double)(x + xmin) - center + 0.5) * inv);
+    w = w < 1.0 ? 1.0 - w : 0.0;
+    ww += w;
+  }
+  for (int x = 0; x < xmax; ++x) {
+    double w = fabs(((double)(x + xmin) - center + 0.5) * inv);
+    w = w < 1.0 ? 1.0 - w : 0.0;
+    if (ww != 0.0) w = w / ww;
+    k[x] = (int)(w < 0.0 ? -0.5 + w * (double)(1 << PRECISION_BITS) : 0.5 + w * (double)(1 << PRECISION_BITS));
+  }
+  for (int x = xmax; x < zero_to; ++x) k[x] = 0;
+  bnd[0] = xmin;
+  bnd[1] = xmax;
+}
+
+__global__ __launch_bounds__(256) void resample_coeffs_kernel(int in_size, int out_size, int ksize, int* __restrict__ bounds,
+                                                              int* __restrict__ kk) {
+  const int xx = blockIdx.x * 256 + threadIdx.x;
+  if (xx < out_size) axis_row(in_size, out_size, xx, ksize, ksize, bounds + 2 * xx, kk + (int64_t)xx * ksize);
+}
+
+// LDS (ints): bh [Wo][2] | kh [Wo][ksh_cap] | bv [R][2] | kv [R][ksv_cap] | tmp [cap_rows][Wo] (RGBx words).  An image's
+// tables use its own ksize as the row stride (odd: consecutive columns fall on different banks).
+__global__ __launch_bounds__(256) void resize_ragged_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                            const int64_t* __restrict__ offsets,
+                                                            const int32_t* __restrict__ sizes,
+                                                            const uint8_t* __restrict__ flip, float* __restrict__ dst, int Ho,
+                                                            int Wo, int R, int nbands, int ksh_cap, int ksv_cap, int cap_rows,
+                                                            float m0, float m1, float m2, float s0, float s1, float s2) {
+  extern __shared__ __attribute__((aligned(16))) int ragged_lds[];
+  int* bh = ragged_lds;
+  int* kh = bh + 2 * Wo;
+  int* bv = kh + Wo * ksh_cap;
+  int* kv = bv + 2 * R;
+  uint32_t* tmp = (uint32_t*)(kv + R * ksv_cap);
+  const int tid = threadIdx.x;
+  const int64_t n = blockIdx.x / nbands;
+  const int band = blockIdx.x - (int)n * nbands;
+  const int Hs = sizes[2 * n], Ws = sizes[2 * n + 1];
+  const int64_t off = offsets[n];
+  // the device tables are the caller's copy of what the host checked; a copy that disagrees leaves the image unwritten
+  // rather than reading or writing outside the buffers (block-uniform: no barrier is skipped by part of a block)
+  if (Hs < 1 || Ws < 1 || off < 0 || off + (int64_t)Hs * Ws * 3 > src_bytes) return;
+  const int ksh = axis_ksize(Ws, Wo), ksv = axis_ksize(Hs, Ho);
+  if (ksh > ksh_cap || ksv > ksv_cap || ksv > cap_rows) return;
+  const uint8_t* img = src + off;
+  const int y0 = band * R, y1 = min(y0 + R, Ho);
+  for (int i = tid; i < Wo + (y1 - y0); i += 256) {
+    if (i < Wo) axis_row(Ws, Wo, i, ksh, 0, bh + 2 * i, kh + i * ksh);
+    else axis_row(Hs, Ho, y0 + (i - Wo), ksv, 0, bv + 2 * (i - Wo), kv + (i - Wo) * ksv);
+  }
+  __syncthreads();
+  const bool flipped = flip != nullptr && flip[n];
+  const int64_t plane = (int64_t)Ho * Wo;
+  float* out = dst + n * 3 * plane;
+  int g0 = y0;
+  while (g0 < y1) {
+    // the output rows g0 .. g1 whose source rows rb .. rb + rows fit the LDS rows (first index and end both grow with yy)
+    const int rb = bv[2 * (g0 - y0)];
+    int g1 = g0 + 1;
+    while (g1 < y1 && bv[2 * (g1 - y0)] + bv[2 * (g1 - y0) + 1] - rb <= cap_rows) ++g1;
+    const int rows = min(bv[2 * (g1 - 1 - y0)] + bv[2 * (g1 - 1 - y0) + 1] - rb, cap_rows);
+    for (int i = tid; i < rows * Wo; i += 256) {          // horizontal pass: lanes along the output columns
+      const int r = i / Wo, xx = i - r * Wo;
+      const int xmin = bh[2 * xx], cnt = bh[2 * xx + 1];
+      const uint8_t* p = img + ((int64_t)(rb + r) * Ws + xmin) * 3;
+      const int* k = kh + xx * ksh;
+      int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
+      for (int x = 0; x < cnt; ++x) {
+        const int w = k[x];
+        a0 += p[3 * x] * w;
+        a1 += p[3 * x + 1] * w;
+        a2 += p[3 * x + 2] * w;
+      }
+      tmp[i] = (uint32_t)clip8(a0) | ((uint32_t)clip8(a1) << 8) | ((uint32_t)clip8(a2) << 16);
+    }
+    __syncthreads();
+    for (int i = tid; i < (g1 - g0) * Wo; i += 256) {     // vertical pass, flip, ToTensor, Normalize
+      const int j = i / Wo, xx = i - j * Wo;
+      const int yy = g0 + j;
+      const int ymin = bv[2 * (yy - y0)] - rb, cnt = min(bv[2 * (yy - y0) + 1], rows - ymin);
+      const int* k = kv + (yy - y0) * ksv;
+      const uint32_t* q = tmp + ymin * Wo + xx;
+      int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
+      for (int y = 0; y < cnt; ++y) {
+        const int w = k[y];
+        const uint32_t v = q[y * Wo];
+        a0 += (int)(v & 255u) * w;
+        a1 += (int)((v >> 8) & 255u) * w;
+        a2 += (int)((v >> 16) & 255u) * w;
+      }
+      const uint8_t u0 = clip8(a0), u1 = clip8(a1), u2 = clip8(a2);
+      const int xo = flipped ? Wo - 1 - xx : xx;
+      float* o = out + (int64_t)yy * Wo + xo;
+      o[0] = ((float)u0 / 255.0f - m0) / s0;          // the float expression of resize_v_norm_kernel
+      o[plane] = ((float)u1 / 255.0f - m1) / s1;
+      o[2 * plane] = ((float)u2 / 255.0f - m2) / s2;
+    }
+    __syncthreads();
+    g0 = g1;
+  }
+}
+
 }  // namespace ieee
 
 using namespace ieee;
@@ -368,4 +509,79 @@ extern "C" int ieee_augment_normalize(const uint8_t* src, float* dst, uint8_t* t
   IEEE_TRY(launch_status("augment_final_kernel"));
   if (launches) *launches = count + 1;
   return 0;
+}
+
+constexpr int RAGGED_MAX_SIDE = 4096;
+constexpr int64_t RAGGED_LDS_BYTES = 64 * 1024;
+
+extern "C" int ieee_resample_ksize(int64_t in_size, int64_t out_size) {
+  if (in_size < 1 || in_size > RAGGED_MAX_SIDE || out_size < 1 || out_size > RAGGED_MAX_SIDE) return 0;
+  return axis_ksize((int)in_size, (int)out_size);
+}
+
+extern "C" int ieee_resample_coeffs(int64_t in_size, int64_t out_size, int32_t* bounds, int32_t* kk, int64_t ksize,
+                                    void* stream) {
+  IEEE_REQUIRE(bounds && kk, "resample_coeffs: null pointer");
+  IEEE_REQUIRE(in_size >= 1 && in_size <= RAGGED_MAX_SIDE && out_size >= 1 && out_size <= RAGGED_MAX_SIDE,
+               "resample_coeffs: sizes of 1 .. 4096");
+  IEEE_REQUIRE(ksize == axis_ksize((int)in_size, (int)out_size), "resample_coeffs: ksize is not ieee_resample_ksize(in, out)");
+  resample_coeffs_kernel<<<(unsigned)cdiv(out_size, 256), 256, 0, (hipStream_t)stream>>>((int)in_size, (int)out_size,
+                                                                                        (int)ksize, bounds, kk);
+  return launch_status("resample_coeffs_kernel");
+}
+
+extern "C" int ieee_resize_normalize_ragged(const uint8_t* src, int64_t src_bytes, const int64_t* offsets,
+                                            const int32_t* sizes, const uint8_t* flip, const int64_t* host_offsets,
+                                            const int32_t* host_sizes, float* dst, int64_t N, int64_t Ho, int64_t Wo,
+                                            const float* mean3, const float* std3, int* launches, void* stream) {
+  if (launches) *launches = 0;
+  IEEE_REQUIRE(N >= 0, "resize_normalize_ragged: negative image count");
+  if (N == 0) return IEEE_OK;
+  IEEE_REQUIRE(src && offsets && sizes && host_offsets && host_sizes && dst && mean3 && std3,
+               "resize_normalize_ragged: null pointer");
+  IEEE_REQUIRE(Ho >= 1 && Ho <= RAGGED_MAX_SIDE && Wo >= 1 && Wo <= RAGGED_MAX_SIDE,
+               "resize_normalize_ragged: output sides of 1 .. 4096");
+  int ksh_cap = 3, ksv_cap = 3;
+  double vscale = 0.0;
+  for (int64_t i = 0; i < N; ++i) {
+    const int64_t hs = host_sizes[2 * i], ws = host_sizes[2 * i + 1], off = host_offsets[i];
+    IEEE_REQUIRE(hs >= 1 && ws >= 1, "resize_normalize_ragged: image %lld is empty (%lld x %lld)", (long long)i, (long long)hs,
+                 (long long)ws);
+    if (hs > RAGGED_MAX_SIDE || ws > RAGGED_MAX_SIDE) {
+      set_error(IEEE_ERR_UNSUPPORTED, "resize_normalize_ragged: image %lld is %lld x %lld; source sides of 1 .. 4096 are supported",
+                (long long)i, (long long)hs, (long long)ws);
+      return IEEE_ERR_UNSUPPORTED;
+    }
+    IEEE_REQUIRE(off >= 0 && off + hs * ws * 3 <= src_bytes, "resize_normalize_ragged: image %lld lies outside the %lld source bytes",
+                 (long long)i, (long long)src_bytes);
+    ksh_cap = std::max(ksh_cap, axis_ksize((int)ws, (int)Wo));
+    ksv_cap = std::max(ksv_cap, axis_ksize((int)hs, (int)Ho));
+    vscale = std::max(vscale, (double)hs / (double)Ho);
+  }
+  // the band height: the largest of 16, 8, .. 1 output rows whose tables leave LDS rows for one output row's window at least
+  const double vsupport = std::max(vscale, 1.0);
+  int R = 16;
+  int64_t cap_rows = 0, fixed = 0;
+  for (;; R >>= 1) {
+    fixed = 4 * (2 * Wo + Wo * ksh_cap + 2 * (int64_t)R + (int64_t)R * ksv_cap);
+    cap_rows = fixed < RAGGED_LDS_BYTES ? (RAGGED_LDS_BYTES - fixed) / (4 * Wo) : 0;
+    if (cap_rows >= ksv_cap || R == 1) break;
+  }
+  if (cap_rows < ksv_cap) {
+    set_error(IEEE_ERR_UNSUPPORTED, "resize_normalize_ragged: the tables of a %lld x %lld output for these sources (%d and %d taps) "
+              "and one output row's window do not fit 64 KiB of LDS", (long long)Ho, (long long)Wo, ksh_cap, ksv_cap);
+    return IEEE_ERR_UNSUPPORTED;
+  }
+  // no more LDS rows than the tallest band reads (an upper bound; the kernel splits a band that needs more than it got)
+  const int64_t need = (int64_t)ceil((R - 1) * vscale + 2.0 * vsupport) + 2;
+  cap_rows = std::max<int64_t>(ksv_cap, std::min(cap_rows, need));
+  const int64_t nbands = (Ho + R - 1) / R;
+  IEEE_REQUIRE(N * nbands <= 0x7fffffffLL, "resize_normalize_ragged: too many images");
+  const size_t lds = (size_t)(fixed + cap_rows * 4 * Wo);
+  resize_ragged_kernel<<<(unsigned)(N * nbands), 256, lds, (hipStream_t)stream>>>(
+      src, src_bytes, offsets, sizes, flip, dst, (int)Ho, (int)Wo, R, (int)nbands, ksh_cap, ksv_cap, (int)cap_rows, mean3[0],
+      mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  IEEE_TRY(launch_status("resize_ragged_kernel"));
+  if (launches) *launches = 1;
+  return IEEE_OK;
 }

@@ -5,7 +5,10 @@ decisions; the pixels are resized, flipped, scaled and normalised by ieee_resize
 what torchvision.transforms does through Pillow on the CPU.
 The reference's other train augmentations -- random_crop (Random2DTranslation), color_jitter (torchvision ColorJitter
 with brightness 0.2 / contrast 0.15) and random_erase (RandomErasing) -- are drawn on the host into an AugmentPlan
-(draw_plan) and applied on the GPU by ieee_augment_normalize ("Train augmentations on the device")."""
+(draw_plan) and applied on the GPU by ieee_augment_normalize ("Train augmentations on the device").
+A list of images of MIXED sizes (detector crops, datasets that are not one size) needs no host tables at all: pack_ragged
+packs it into one byte buffer and ieee_resize_normalize_ragged resizes the whole batch in one launch, computing Pillow's
+coefficients on the device (DeviceTransform.ragged; DESIGN.md, "Ragged batches")."""
 import math
 import random as _random
 
@@ -61,6 +64,68 @@ def resample_tables(hs, ws, ho, wo):
         _TABLE_CACHE[key] = dict(need_h=wo != ws, need_v=ho != hs, bounds_h=bh, kk_h=kh, ksize_h=ksh, bounds_v=bv,
                                  kk_v=kv, ksize_v=ksv, ybox_first=y0, tmp_rows=int(bv[ho - 1, 0] + bv[ho - 1, 1]) - y0)
     return _TABLE_CACHE[key]
+
+
+RAGGED_ALIGN = 16     # pack_ragged starts every image on a multiple of this many bytes
+
+
+class _Staging(object):
+    """the packed bytes of one ragged batch on their way to the device: one buffer, pinned where there is a GPU and grown by
+    doubling; `done` is recorded behind the copy out of it and waited for before the host writes it again.  Owned by ONE
+    caller at a time, like the flip and plan rings: a DeviceTransform keeps its own, pack_ragged the module's.  (Not a
+    threading.local: a child forked from another thread -- a decode worker started by the prefetch thread -- destroys the
+    thread-local objects of every other thread, and freeing pinned memory or an event there takes the child down.)"""
+
+    def __init__(self):
+        self.buf = self.done = self.done_on = None
+
+    def room(self, nbytes):
+        if self.done is not None:
+            self.done.synchronize()
+        if self.buf is None or self.buf.numel() < nbytes:
+            size = max(1 << 20, 1 << int(nbytes - 1).bit_length())
+            self.buf = torch.empty(size, dtype=torch.uint8)
+            if torch.cuda.is_available():
+                self.buf = self.buf.pin_memory()
+        return self.buf
+
+
+_STAGING = _Staging()       # pack_ragged's own
+
+
+def _as_rgb_u8(im):
+    im = np.asarray(im)
+    if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
+        raise ValueError("expected uint8 HxWx3 images (PIL 'RGB'), got %s %s" % (im.dtype, im.shape))
+    return im
+
+
+def _pack_ragged(images, staging, tail=0):
+    """pack_ragged into `staging`, with `tail` spare bytes behind the images (16-byte aligned):
+    -> (the staging tensor, image bytes, offsets, sizes)"""
+    arrays = [_as_rgb_u8(im) for im in images]
+    n = len(arrays)
+    sizes = np.zeros((n, 2), dtype=np.int32)
+    offsets = np.zeros(n, dtype=np.int64)
+    at = 0
+    for i, a in enumerate(arrays):
+        sizes[i] = a.shape[:2]
+        offsets[i] = at
+        at += -(-a.size // RAGGED_ALIGN) * RAGGED_ALIGN
+    stage = staging.room(at + tail)
+    flat = stage.numpy()
+    for a, off in zip(arrays, offsets):
+        flat[off:off + a.size].reshape(a.shape)[...] = a           # one pass, strided sources included
+    return stage, at, offsets, sizes
+
+
+def pack_ragged(images):
+    """N uint8 HxWx3 images (arrays, PIL 'RGB' images; any strides), each of its own size -> (buffer uint8 [bytes], offsets
+    int64 [N], sizes int32 [N, 2] = (H, W)): image i is the tightly packed [H][W][3] block at buffer[offsets[i]:]; every image
+    starts on a multiple of 16 bytes.  Host only.  `buffer` is a view of ONE staging buffer (pinned where there is a GPU)
+    that the next call overwrites: one caller at a time."""
+    stage, nbytes, offsets, sizes = _pack_ragged(images, _STAGING)
+    return stage.numpy()[:nbytes], offsets, sizes
 
 
 PLAN_WORDS = 12       # int32 words per image of the packed plan (ieee_augment_normalize; include/ieee_amd.h)
@@ -153,6 +218,7 @@ class DeviceTransform(object):
         self.augments = self.crop or self.jitter or self.erase      # anything beyond the flip: the plan path
         self.needs_py_rng = self.crop or self.erase                 # stages that draw from python's `random`
         self.last_launches = None                                   # kernel launches of the last augmented call
+        self.last_ragged_launches = None                            # kernel launches of the last ragged call
         self.mean = np.asarray(IMAGENET_MEAN if norm_mean is None or norm_std is None else norm_mean, dtype=np.float32)
         self.std = np.asarray(IMAGENET_STD if norm_mean is None or norm_std is None else norm_std, dtype=np.float32)
         self.device = device
@@ -336,6 +402,42 @@ class DeviceTransform(object):
         self.last_launches = launches
         return out
 
+    def ragged(self, images, flips=None):
+        """Resize -> flip -> ToTensor -> Normalize of N images of ANY mix of sizes -> float32 [N, 3, height, width] on the
+        device: the bits of the one-size path, from one host-to-device copy (the packed pixels with the offset / size / flip
+        tables behind them) and one ieee_resize_normalize_ragged call (one launch; Pillow's coefficients are computed on the
+        device, nothing is cached per size).  flips: as in __call__ (drawn when None).  The train augmentations beyond the
+        flip are not part of this path."""
+        lib = _lib.require_gpu()
+        dev = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        n = len(images)
+        out = torch.empty((n, 3, self.height, self.width), dtype=torch.float32, device=dev)
+        if n == 0:
+            return out
+        flips = self.draw_flips(n) if flips is None else np.asarray(flips, dtype=np.uint8)
+        if len(flips) != n:
+            raise ValueError("%d flip decisions for %d images" % (len(flips), n))
+        staging = self.__dict__.setdefault("_staging", _Staging())      # this transform's own, like its flip and plan rings
+        stage, nbytes, offsets, sizes = _pack_ragged(images, staging, tail=17 * n)
+        flat = stage.numpy()
+        flat[nbytes:nbytes + 8 * n] = offsets.view(np.uint8)                    # offsets | sizes | flips, behind the pixels
+        flat[nbytes + 8 * n:nbytes + 16 * n] = sizes.reshape(-1).view(np.uint8)
+        flat[nbytes + 16 * n:nbytes + 17 * n] = flips
+        src = stage[:nbytes + 17 * n].to(dev, non_blocking=True)
+        if staging.done is None or staging.done_on != dev:        # (room() has waited for the event this one replaces)
+            staging.done, staging.done_on = torch.cuda.Event(), dev
+        staging.done.record(torch.cuda.current_stream(dev))
+        base = src.data_ptr()
+        mean = (_lib.ctypes.c_float * 3)(*self.mean.tolist())
+        std = (_lib.ctypes.c_float * 3)(*self.std.tolist())
+        launches = _lib.c_int(0)
+        _lib.check(lib.ieee_resize_normalize_ragged(
+            _lib.c_void_p(base), nbytes, _lib.c_void_p(base + nbytes), _lib.c_void_p(base + nbytes + 8 * n),
+            _lib.c_void_p(base + nbytes + 16 * n), _lib.c_void_p(offsets.ctypes.data), _lib.c_void_p(sizes.ctypes.data),
+            _lib.ptr(out), n, self.height, self.width, mean, std, _lib.ctypes.byref(launches), _lib.stream()))
+        self.last_ragged_launches = int(launches.value)
+        return out
+
     def __call__(self, images, flips=None, plan=None):
         """flips: the flip decisions (else drawn); plan: an AugmentPlan with every decision (else drawn by draw_plan).  With
         both, `flips` replaces the plan's flips.  Without augmentations beyond the flip only the flips of a plan are used."""
@@ -393,21 +495,21 @@ class DeviceTransform(object):
             if im.ndim != 3 or im.shape[2] != 3 or im.dtype != np.uint8:
                 raise ValueError("expected uint8 HxWx3 images (PIL 'RGB'), got %s %s" % (im.dtype, im.shape))
             groups.setdefault(im.shape[:2], []).append(i)
+        if len(groups) > 1:
+            # mixed sizes: one copy and one launch for the whole list, no table per size (the same bits)
+            return self.ragged(images, flips)
+        (hs, ws), = groups
         mean = (_lib.ctypes.c_float * 3)(*self.mean.tolist())
         std = (_lib.ctypes.c_float * 3)(*self.std.tolist())
-        for (hs, ws), idx in groups.items():
-            t, bh, kh, bv, kv = self._tables_on(dev, hs, ws)
-            src = torch.from_numpy(np.stack([np.ascontiguousarray(images[i]) for i in idx])).to(dev, non_blocking=True)
-            fl = torch.from_numpy(flips[idx].copy()).to(dev)
-            dst = out if len(groups) == 1 else torch.empty((len(idx), 3, self.height, self.width), dtype=torch.float32, device=dev)
-            tmp = torch.empty((len(idx), t["tmp_rows"], self.width, 3), dtype=torch.uint8, device=dev) if t["need_h"] else None
-            _lib.check(lib.ieee_resize_flip_normalize(
-                _lib.ptr(src), _lib.ptr(dst), _lib.ptr(tmp) if tmp is not None else None, len(idx), hs, ws, self.height,
-                self.width, _lib.ptr(bh) if t["need_h"] else None, _lib.ptr(kh) if t["need_h"] else None, t["ksize_h"],
-                _lib.ptr(bv) if t["need_v"] else None, _lib.ptr(kv) if t["need_v"] else None, t["ksize_v"],
-                t["ybox_first"], t["tmp_rows"], _lib.ptr(fl), mean, std, _lib.stream()))
-            if dst is not out:
-                out[torch.as_tensor(idx, device=dev)] = dst
+        t, bh, kh, bv, kv = self._tables_on(dev, hs, ws)
+        src = torch.from_numpy(np.stack([np.ascontiguousarray(im) for im in images])).to(dev, non_blocking=True)
+        fl = torch.from_numpy(flips.copy()).to(dev)
+        tmp = torch.empty((n, t["tmp_rows"], self.width, 3), dtype=torch.uint8, device=dev) if t["need_h"] else None
+        _lib.check(lib.ieee_resize_flip_normalize(
+            _lib.ptr(src), _lib.ptr(out), _lib.ptr(tmp) if tmp is not None else None, n, hs, ws, self.height,
+            self.width, _lib.ptr(bh) if t["need_h"] else None, _lib.ptr(kh) if t["need_h"] else None, t["ksize_h"],
+            _lib.ptr(bv) if t["need_v"] else None, _lib.ptr(kv) if t["need_v"] else None, t["ksize_v"],
+            t["ybox_first"], t["tmp_rows"], _lib.ptr(fl), mean, std, _lib.stream()))
         return out
 
 

@@ -702,6 +702,34 @@ int ieee_augment_normalize(const uint8_t* src, float* dst, uint8_t* tmp, int64_t
                            const int32_t* big_bounds_v, const int32_t* big_kk_v, int64_t big_ksize_v,
                            const float* mean3, const float* std3, int* launches, void* stream);
 
+/* The resize chain above (no augmentation) for a RAGGED batch: N decoded uint8 RGB images, each with its own size, in ONE
+ * launch and without host tables.  src: device bytes, src_bytes long; image i is the tightly packed [Hs_i][Ws_i][3] block at
+ * byte offsets[i] (gaps between images are allowed); sizes [N][2] int32 = (Hs_i, Ws_i); flip [N] bytes or NULL: all three
+ * DEVICE arrays.  host_offsets / host_sizes: HOST copies of the same two tables -- every image is checked against
+ * 1 <= side <= 4096 and against src_bytes before anything is launched (a device table that disagrees with its host copy
+ * leaves that image's output unwritten; nothing is read or written out of bounds).  dst [N][3][Ho][Wo] fp32; mean3 / std3:
+ * HOST pointers to 3 floats.  Per image the arithmetic is ieee_resize_flip_normalize's, bit for bit: Pillow's two-pass
+ * 8-bit bilinear resampler, horizontal pass first and only over the source rows the vertical pass reads, the intermediate
+ * rounded to 8 bits, then flip, / 255, (x - mean) / std; an axis that keeps its size gets identity weight rows, which
+ * return what skipping the pass returns.  Pillow's coefficients (precompute_coeffs + normalize_coeffs_8bpc: fp64, the
+ * scale from the float32 of the size, weights trunc(+-0.5 + k * 2^22)) are computed on the device by every workgroup for
+ * the rows and columns it needs.  One workgroup per (image, band of up to 16 output rows) keeps the band's horizontal
+ * intermediate in LDS (at most 64 KiB with the tables; the band height is halved until one output row's window fits).
+ * Returns IEEE_ERR_UNSUPPORTED before any launch for a source side above 4096 or tables that do not fit (a 1-row band of a
+ * very wide output from very large sources), IEEE_ERR_BAD_ARG for anything malformed; N = 0 is IEEE_OK and launches
+ * nothing.  1 launch whatever N and the sizes are; no workspace, no allocation, no host synchronisation.
+ * launches: HOST int, receives the launch count, or NULL. */
+int ieee_resize_normalize_ragged(const uint8_t* src, int64_t src_bytes, const int64_t* offsets, const int32_t* sizes,
+                                 const uint8_t* flip, const int64_t* host_offsets, const int32_t* host_sizes, float* dst,
+                                 int64_t N, int64_t Ho, int64_t Wo, const float* mean3, const float* std3, int* launches,
+                                 void* stream);
+/* The device coefficient function of ieee_resize_normalize_ragged run over a whole axis: bounds [out_size][2] int32 =
+ * (first source index, count) and kk [out_size][ksize] int32 (22-bit fixed point, zero past count), both DEVICE; what
+ * _axis_tables of ieee_amd/data/transforms.py computes on the host.  ksize must be ieee_resample_ksize(in_size, out_size)
+ * (host only; 0 for sizes outside 1 .. 4096).  1 launch. */
+int ieee_resample_ksize(int64_t in_size, int64_t out_size);
+int ieee_resample_coeffs(int64_t in_size, int64_t out_size, int32_t* bounds, int32_t* kk, int64_t ksize, void* stream);
+
 /* ---- whole-network executor --------------------------------------------------- */
 /* One handle = IEEE3modalPart (ieee3modalPart.py:286-523) for a fixed batch / image size / dtype.
  * The caller owns three flat fp32 buffers laid out like the reference's state_dict: parameters,
