@@ -258,6 +258,12 @@ class DeviceLoader(object):
         recs = self.dataset.data
         return [([recs[i][1] for i in idx], [recs[i][2] for i in idx]) for idx in self._all]
 
+    def batch_timeids(self):
+        """[timeids] of every global batch, in loader order, from the records alone (0 where a record carries none)"""
+        assert self._owned is not None, "batch_timeids() is for rank-sharded sequential loaders"
+        recs = self.dataset.data
+        return [[recs[i][3] if len(recs[i]) > 3 else 0 for i in idx] for idx in self._all]
+
     def __len__(self):
         return len(self.loader)
 

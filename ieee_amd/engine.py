@@ -257,6 +257,10 @@ class Engine(object):
         ranks each one runs the forward for every world-th batch and one all-gather completes the matrix."""
         world, me = ddp.world_size(), ddp.rank()
         mine, rows, pids, cams = {}, [], [], []
+        # the time ids of every batch this rank walked, kept beside the return value (the cuhk03 protocol filters on
+        # them): self._timeids_seen is the whole loader's array after the call, or None when batches were not seen
+        tids = {}
+        self._timeids_seen = None
         # a loader that is itself sharded over the ranks (ieee_amd.data.DeviceLoader(rank=, world=)) decodes only this
         # rank's batches and knows every batch's labels from its records; any other loader is walked in full and the
         # foreign batches are skipped before the forward
@@ -266,11 +270,14 @@ class Engine(object):
                 pids.append(np.asarray(p).reshape(-1))
                 cams.append(np.asarray(c).reshape(-1))
                 rows.append(len(p))
+            if hasattr(loader, 'batch_timeids'):
+                tids = {b: np.asarray(tt).reshape(-1) for b, tt in enumerate(loader.batch_timeids())}
         for b, data in enumerate(loader):
             imgs, p, c, timeids = self.parse_data_for_eval(data)
             if presharded:
                 b = int(data['batch_index'])
             else:
+                tids[b] = np.asarray(timeids).reshape(-1)
                 p, c = np.asarray(p).reshape(-1), np.asarray(c).reshape(-1)
                 pids.append(p)
                 cams.append(c)
@@ -289,6 +296,8 @@ class Engine(object):
             width = some.shape[1] if some is not None else 2304
             device = some.device if some is not None else torch.device('cuda' if self.use_gpu else 'cpu')
             feats = ddp.gather_feature_batches(mine, rows, width, device)
+        if len(tids) == len(rows):
+            self._timeids_seen = np.concatenate([tids[b] for b in range(len(rows))]) if rows else np.zeros(0)
         return feats, np.concatenate(pids), np.concatenate(cams)
 
     @torch.no_grad()
@@ -312,9 +321,11 @@ class Engine(object):
             ddp.sync_replicas(self.model, buffers_only=True)       # DataParallel evaluates with GPU 0's statistics
         say('Extracting features from query set ...')
         qf, q_pids, q_camids = self._descriptors(query_loader, clock)
+        q_timeids = getattr(self, '_timeids_seen', None)     # a patched _descriptors leaves none: camera filter only
         say('Done, obtained {}-by-{} matrix'.format(qf.size(0), qf.size(1)))
         say('Extracting features from gallery set ...')
         gf, g_pids, g_camids = self._descriptors(gallery_loader, clock)
+        g_timeids = getattr(self, '_timeids_seen', None)
         say('Done, obtained {}-by-{} matrix'.format(gf.size(0), gf.size(1)))
         say('Speed: {:.4f} sec/batch'.format(clock.avg))
         if normalize_feature:
@@ -337,7 +348,13 @@ class Engine(object):
                 distmat = re_ranking(distmat, compute_distance_matrix(qf, qf, dist_metric),
                                      compute_distance_matrix(gf, gf, dist_metric))
             say('Computing CMC and mAP for {}'.format(dataset_name))
-            cmc, mAP = evaluate_rank(distmat, q_pids, g_pids, q_camids, g_camids, use_metric_cuhk03=use_metric_cuhk03)
+            if use_metric_cuhk03:   # rank.py:24-100 filters on the time ids as well
+                if q_timeids is None or g_timeids is None:
+                    q_timeids = g_timeids = None
+                cmc, mAP = evaluate_rank(distmat, q_pids, g_pids, q_camids, g_camids, use_metric_cuhk03=True,
+                                         q_timeids=q_timeids, g_timeids=g_timeids)
+            else:
+                cmc, mAP = evaluate_rank(distmat, q_pids, g_pids, q_camids, g_camids, use_metric_cuhk03=use_metric_cuhk03)
         say('** Results **')
         say('mAP: {:.2%}'.format(mAP))
         say('CMC curve')

@@ -105,6 +105,28 @@ int ieee_rank_topk(const float* distmat, int64_t ldd, int64_t num_q, int64_t num
                    const int32_t* q_pids, const int32_t* g_pids, const int32_t* q_camids,
                    const int32_t* g_camids, int exclude_same_cam, int64_t k, int32_t* out_idx,
                    float* out_dist, void* stream);
+/* CUHK03 single-gallery-shot protocol, torchreid/metrics/rank.py:24-100 (eval_cuhk03 with the time-id filter): the
+ * EXPECTED curve of the protocol's random draw (one gallery image per identity, uniformly), not a 10-sample estimate
+ * of it.  distmat [num_q][num_g] fp32 (row stride ldd >= num_g); q_pids / g_pids int32; q_keys / g_keys int32, one
+ * word per (camera, time id) pair, equal pairs equal words on both sides.  Per query the gallery is ordered on
+ * (distance, gallery index), -0.0 equal to +0.0, NaN after +inf; entries with the query's identity AND key are dropped;
+ * a query without a kept true match is skipped.  With T the kept true matches and, for every other identity j of n_j
+ * images, c_j(t) of them before true match t:
+ *   cmc[r] = (1 / |T|) sum_t P(sum_j B_j(t) <= r),  B_j(t) ~ Bernoulli(c_j(t) / n_j) independent,
+ * by the recurrence pmf'[k] = pmf[k](1 - p) + pmf[k-1] p over the identities in ascending-pid order, in float64.
+ * A query that sees fewer than max_rank identities has 1.0 in the tail of its curve.  Outputs (device):
+ *   cmc     [num_q][max_rank] float64   the per-query curve (zeros when skipped)
+ *   ap      [num_q] float64             average precision of the kept list (-1 when skipped)
+ *   summary [max_rank+2] float64        the curves summed over the valid queries, num_valid_q, the AP sum
+ * The host shim forms cmc = float32(sum / num_valid) and mAP = ap_sum / num_valid.  Every sum has one fixed order and
+ * there are no floating-point atomics: two calls give the same bits.  work: ieee_rank_cuhk03_workspace_bytes(num_g)
+ * bytes (device, 4-byte aligned), the gallery grouped by identity.  1 <= max_rank <= 1024 (not clamped to num_g),
+ * ldd >= num_g and a large enough workspace, else IEEE_ERR_BAD_ARG before any launch.  No host sync inside. */
+int64_t ieee_rank_cuhk03_workspace_bytes(int64_t num_g);
+int ieee_rank_cuhk03(const float* distmat, int64_t ldd, int64_t num_q, int64_t num_g,
+                     const int32_t* q_pids, const int32_t* g_pids, const int32_t* q_keys,
+                     const int32_t* g_keys, int64_t max_rank, double* cmc, double* ap, double* summary,
+                     void* work, int64_t work_bytes, void* stream);
 
 /* ---- activation maps (tools/visualize_actmap.py) --------------------------- */
 /* tools/visualize_actmap.py:84-88: outputs = (outputs**2).sum(1); F.normalize(outputs.view(b, h*w), p=2, dim=1).

@@ -55,6 +55,8 @@ def main():
     ap.add_argument("--save-dir", default="")
     ap.add_argument("--transforms", default="random_flip", help="comma-separated train augmentations (the reference's "
                     "build_transforms names): random_flip, random_crop, color_jitter, random_erase")
+    ap.add_argument("--cuhk03", action="store_true", help="evaluate with the CUHK03 single-gallery-shot protocol (expected CMC "
+                    "of one drawn image per gallery identity; entries of the query's identity, camera and time id removed)")
     args = ap.parse_args()
 
     if args.gpus > 1 and ddp.env_world()[0] == 1:
@@ -95,8 +97,8 @@ def main():
     engine = Image3MEngine(dm, model, optimizer, margin=1, weight_m=1, weight_x=1, scheduler=scheduler, use_gpu=True,
                            label_smooth=True)
     engine.run(save_dir=args.save_dir or os.path.join(tempfile.gettempdir(), "ieee_example_log"), max_epoch=args.epochs,
-               eval_freq=args.eval_freq, print_freq=10, ranks=ranks)
-    mAP = engine.test(ranks=ranks)           # (Engine.run does not evaluate after the last epoch, like the reference)
+               eval_freq=args.eval_freq, print_freq=10, ranks=ranks, use_metric_cuhk03=args.cuhk03)
+    mAP = engine.test(ranks=ranks, use_metric_cuhk03=args.cuhk03)           # (Engine.run does not evaluate after the last epoch, like the reference)
     if rank == 0:
         print("FINAL mAP %.4f after %d epoch(s) on %d rank(s), %d train batches per epoch" % (mAP, args.epochs, world, len(train)))
     if world > 1:
