@@ -41,6 +41,8 @@ int launch_status(const char* what);
   } while (0)
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// workspace regions start on 256-byte boundaries
+static inline int64_t align256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
 
 template <typename T> struct DTypeOf;
 template <> struct DTypeOf<float> { static constexpr int value = IEEE_F32; };

@@ -2,6 +2,7 @@
 // GEMM with fused norm epilogue) and Market1501-protocol CMC / mAP.
 // Reference arithmetic: torchreid/metrics/distance.py:49-80, rank.py:103-171.
 #include "gemm_core.h"
+#include "rank_common.h"
 
 namespace ieee {
 
@@ -236,43 +237,11 @@ __global__ __launch_bounds__(256) void split_rows_f16_kernel(const float* __rest
 
 // ---------------------------------------------------------------- CMC / mAP
 constexpr int RANK_CAP = 1024;    // match keys sorted per batch (LDS)
-#ifndef IEEE_RANK_CELLS
-#define IEEE_RANK_CELLS 512
-#endif
-#ifndef IEEE_RANK_UNR
-#define IEEE_RANK_UNR 8
-#endif
-constexpr int RANK_CELLS = IEEE_RANK_CELLS;  // distance cells over the batch's match range
+constexpr int RANK_CELLS = 512;   // distance cells over the batch's match range
+constexpr int RANK_UNR = 8;       // 16-byte loads per thread in flight in rank_query_fast_kernel's stream
 
-__device__ __forceinline__ uint64_t make_key(float d, uint32_t idx) {
-  uint32_t u = __float_as_uint(d);
-  u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;   // total order of IEEE floats
-  return ((uint64_t)u << 32) | idx;
-}
-
-// exclusive scan of one uint per thread over the 256-thread block; returns the
-// exclusive prefix and writes the block total to *total (uses 8 LDS words).
-__device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* wsum, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(inc, o);
-    if (lane >= o) inc += y;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const uint32_t s = wsum[w];
-    if (w < wave) base += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
+// the Market protocol orders on the raw IEEE total order (rank_common.h says why)
+__device__ __forceinline__ uint64_t make_key(float d, uint32_t idx) { return order_key(order_word_raw(d), idx); }
 
 // Cell of a distance on the uniform grid laid over [dmin, dmax] of a batch's sorted match keys.  Every step
 // (subtract a constant, multiply by a non-negative constant, min, truncate) is monotone under rounding, so
@@ -282,10 +251,57 @@ __device__ __forceinline__ uint32_t rank_cell(float d, float dmin, float scale) 
   return (uint32_t)(int)fminf((d - dmin) * scale, (float)(RANK_CELLS - 1));   // NaN -> last cell
 }
 
-__device__ __forceinline__ float key_dist(uint64_t key) {
-  uint32_t u = (uint32_t)(key >> 32);
-  u ^= (u >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-  return __uint_as_float(u);
+// ---- the batch core of the two query kernels: what they do with a batch of nb <= RANK_CAP match keys is the same;
+// how the keys are collected, what an element adds to hist and how the removed entries leave it is theirs.
+struct RankGrid {
+  uint64_t kmin, kmax;       // the batch's smallest and largest match key
+  float dmin, dmax, scale;   // their distances, and cells per unit of distance
+  uint32_t hlen;             // words of hist in use: slots 0 .. RANK_CELLS + nb + 1
+};
+
+// keys[0, nb) are the batch's match keys in any order, written by the caller and not yet synchronised (the first
+// barrier is lds_bitonic_sort's; it also covers what the caller cleared just before the call).  On return the keys are
+// sorted, hist is zero up to its scan slack, cellinfo[c] = first key index of cell c | keys in the cell << 16, and all
+// of it is visible to the block.
+__device__ __forceinline__ RankGrid rank_prepare_batch(uint64_t* keys, uint32_t nb, uint32_t* hist, uint32_t* cellinfo,
+                                                       uint32_t* wsum) {
+  const uint32_t t = threadIdx.x;
+  RankGrid g;
+  g.hlen = RANK_CELLS + nb + 2;
+  for (uint32_t i = t; i < g.hlen + 512; i += 256) hist[i] = 0;
+  for (uint32_t i = t; i < RANK_CELLS; i += 256) cellinfo[i] = 0;
+  lds_bitonic_sort<256>(keys, nb);
+  g.kmin = keys[0];
+  g.kmax = keys[nb - 1];
+  g.dmin = key_dist(g.kmin);
+  g.dmax = key_dist(g.kmax);
+  g.scale = (float)RANK_CELLS / (g.dmax - g.dmin);
+  if (!(g.scale < 1e30f)) g.scale = 0.f;         // one distinct distance (or inf/NaN): a single cell
+  // count the keys of every cell, then an exclusive scan gives the first key of each
+  for (uint32_t i = t; i < nb; i += 256) atomicAdd(&cellinfo[rank_cell(key_dist(keys[i]), g.dmin, g.scale)], 1u);
+  __syncthreads();
+  constexpr int PER = RANK_CELLS / 256;
+  uint32_t c[PER], sum = 0;
+#pragma unroll
+  for (int e = 0; e < PER; ++e) { c[e] = cellinfo[t * PER + e]; sum += c[e]; }
+  uint32_t tot;
+  uint32_t run = block_scan_excl(sum, wsum, &tot);
+#pragma unroll
+  for (int e = 0; e < PER; ++e) { cellinfo[t * PER + e] = run | (c[e] << 16); run += c[e]; }
+  __syncthreads();
+  return g;
+}
+
+// inclusive prefix sums over hist[0, hlen) in place: a contiguous odd-length span per thread (conflict-free; the spans
+// reach into hist's 512 words of slack, which are zero)
+__device__ __forceinline__ void rank_scan_hist(uint32_t* hist, uint32_t hlen, uint32_t* wsum) {
+  const uint32_t t = threadIdx.x, per = ((hlen + 255) / 256) | 1u;
+  uint32_t sum = 0;
+  for (uint32_t e = 0; e < per; ++e) sum += hist[t * per + e];
+  uint32_t tot;
+  uint32_t run = block_scan_excl(sum, wsum, &tot);
+  for (uint32_t e = 0; e < per; ++e) { run += hist[t * per + e]; hist[t * per + e] = run; }
+  __syncthreads();
 }
 
 // ---- identity buckets: gallery indices grouped by a hash of their identity (counting sort, order inside a bucket
@@ -305,9 +321,7 @@ __global__ __launch_bounds__(1024) void rank_bucket_scan_kernel(int32_t* start, 
   int32_t c[PER], sum = 0;
 #pragma unroll
   for (int e = 0; e < PER; ++e) { c[e] = start[1 + t * PER + e]; sum += c[e]; }
-  int32_t inc = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const int32_t v = __shfl_up(inc, o); if (lane >= o) inc += v; }
+  const int32_t inc = (int32_t)wave_scan_incl((uint32_t)sum);
   if (lane == 63) wsum[wave] = inc;
   __syncthreads();
   int32_t base = 0;
@@ -329,10 +343,6 @@ __global__ __launch_bounds__(256) void rank_bucket_fill_kernel(const int32_t* __
 // hist[slot], slot = 1 + cell + #{match keys < key} being monotone in the key, the removed entries are then
 // subtracted from the slots they were counted in, and the rank of match i is the inclusive prefix sum at
 // 1 + cell_i + i.  A query that does not fit writes first_out = -2 and is left to rank_query_kernel.
-// DBG (measurement only, IEEE_RANK_DBG; wrong results): 1 = the per-element LDS histogram add is replaced by a register
-// sum (what the atomics cost), 2 = the per-element cell-table read is skipped (slot = 1 + cell: what the lookups cost),
-// 3 = both.  LABNOTES R6.5 uses them to split the kernel's LDS-conflict share between the two accesses.
-template <int DBG = 0>
 __global__ __launch_bounds__(256) void rank_query_fast_kernel(const float* distmat, int64_t ldd, int num_g,
                                                               const int32_t* q_pids, const int32_t* g_pids,
                                                               const int32_t* q_camids, const int32_t* g_camids,
@@ -395,43 +405,9 @@ __global__ __launch_bounds__(256) void rank_query_fast_kernel(const float* distm
     if (t == 0) { ap_out[q] = -1.0; first_out[q] = -1; }   // rank.py:140-142: no valid match, query skipped
     return;
   }
-  // ---- bitonic sort of keys[0..np2) ascending, padded with +inf keys
-  uint32_t np2 = 1;
-  while (np2 < nb) np2 <<= 1;
-  for (uint32_t i = nb + t; i < np2; i += 256) keys[i] = ~0ull;
-  const uint32_t hlen = RANK_CELLS + nb + 2;
-  for (uint32_t i = t; i < hlen + 512; i += 256) hist[i] = 0;
-  for (uint32_t i = t; i < RANK_CELLS; i += 256) cellinfo[i] = 0;
-  __syncthreads();
-  for (uint32_t k = 2; k <= np2; k <<= 1) {
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      for (uint32_t i = t; i < np2; i += 256) {
-        const uint32_t l = i ^ j;
-        if (l > i) {
-          const uint64_t a = keys[i], b = keys[l];
-          const bool up = (i & k) == 0;
-          if ((a > b) == up) { keys[i] = b; keys[l] = a; }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  const float dmin = key_dist(keys[0]), dmax = key_dist(keys[nb - 1]);
-  float scale = (float)RANK_CELLS / (dmax - dmin);
-  if (!(scale < 1e30f)) scale = 0.f;             // one distinct distance (or inf/NaN): a single cell
-  for (uint32_t i = t; i < nb; i += 256) atomicAdd(&cellinfo[rank_cell(key_dist(keys[i]), dmin, scale)], 1u);
-  __syncthreads();
-  {
-    constexpr int PER = RANK_CELLS / 256;
-    uint32_t c[PER], sum = 0;
-#pragma unroll
-    for (int e = 0; e < PER; ++e) { c[e] = cellinfo[t * PER + e]; sum += c[e]; }
-    uint32_t tot;
-    uint32_t run = block_scan_excl(sum, wsum, &tot);
-#pragma unroll
-    for (int e = 0; e < PER; ++e) { cellinfo[t * PER + e] = run | (c[e] << 16); run += c[e]; }
-  }
-  __syncthreads();
+  // ---- sort the matches, lay the cell table over them
+  const RankGrid grid = rank_prepare_batch(keys, nb, hist, cellinfo, wsum);
+  const float dmin = grid.dmin, dmax = grid.dmax, scale = grid.scale;
   // slot of an element, or -1 when it lies after every match (no rank depends on it).  Float compares decide
   // whenever they can (d > dmax, d < dmin, a cell without keys); only elements that share a cell with match keys
   // build the 64-bit (distance, index) key.  NaN distances go last, as in numpy's argsort.
@@ -439,7 +415,6 @@ __global__ __launch_bounds__(256) void rank_query_fast_kernel(const float* distm
     if (d > dmax) return -1;
     if (d < dmin) return 0;
     const uint32_t c = rank_cell(d, dmin, scale);
-    if constexpr (DBG == 2 || DBG == 3) return (int)(1 + c);
     const uint32_t ci = cellinfo[c];
     uint32_t lo = ci & 0xffffu;
     if (ci >> 16) {
@@ -455,12 +430,11 @@ __global__ __launch_bounds__(256) void rank_query_fast_kernel(const float* distm
   uint32_t below = 0;
   auto visit = [&](float d, int k) {
     const int sl = slot_of(d, k);
-    if constexpr (DBG == 1 || DBG == 3) { below += (uint32_t)sl; return; }
     if (sl > 0) atomicAdd(&hist[sl], 1u);
     else if (sl == 0) ++below;
   };
-  // ---- stream the row: 4 independent 16-byte loads per thread in flight before any is used
-  constexpr int UNR = IEEE_RANK_UNR;
+  // ---- stream the row: RANK_UNR independent 16-byte loads per thread in flight before any is used
+  constexpr int UNR = RANK_UNR;
   int kdone = 0;
   if (((uintptr_t)row & 15) == 0) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -491,16 +465,7 @@ __global__ __launch_bounds__(256) void rank_query_fast_kernel(const float* distm
     if (sl >= 0) atomicSub(&hist[sl], 1u);
   }
   __syncthreads();
-  // ---- inclusive prefix sums over hist in place: a contiguous odd-length span per thread (conflict-free)
-  {
-    const uint32_t per = ((hlen + 255) / 256) | 1u;
-    uint32_t sum = 0;
-    for (uint32_t e = 0; e < per; ++e) sum += hist[t * per + e];
-    uint32_t tot;
-    uint32_t run = block_scan_excl(sum, wsum, &tot);
-    for (uint32_t e = 0; e < per; ++e) { run += hist[t * per + e]; hist[t * per + e] = run; }
-  }
-  __syncthreads();
+  rank_scan_hist(hist, grid.hlen, wsum);
   double part = 0.0;
   int32_t fmin = 0x7fffffff;
   for (uint32_t i = t; i < nb; i += 256) {
@@ -509,13 +474,7 @@ __global__ __launch_bounds__(256) void rank_query_fast_kernel(const float* distm
     part += (double)(i + 1) / (double)(rank + 1);      // rank.py:156-157; i matches precede match i
     fmin = min(fmin, (int32_t)rank);
   }
-  dsum[t] = part;
-  imin[t] = fmin;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) { dsum[t] += dsum[t + o]; imin[t] = min(imin[t], imin[t + o]); }
-    __syncthreads();
-  }
+  block_tree_sum(part, fmin, dsum, imin, [](int32_t a, int32_t b) { return min(a, b); });
   if (t == 0) {
     ap_out[q] = dsum[0] / (double)nb;                  // rank.py:153-158
     first_out[q] = imin[0];
@@ -582,46 +541,11 @@ __global__ __launch_bounds__(256) void rank_query_kernel(const float* distmat, i
     }
     jstart = base;
     if (nb == 0) continue;   // (jstart advanced to num_g) no match in the remainder
-    // ---- bitonic sort of keys[0..np2) ascending, padded with +inf keys
-    uint32_t np2 = 1;
-    while (np2 < nb) np2 <<= 1;
-    for (uint32_t i = nb + t; i < np2; i += 256) keys[i] = ~0ull;
-    const uint32_t hlen = RANK_CELLS + nb + 2;
-    for (uint32_t i = t; i < hlen + 512; i += 256) hist[i] = 0;
+    // ---- sort the matches, lay the cell table over them (histm is cleared under the same first barrier)
     for (uint32_t i = t; i <= nb; i += 256) histm[i] = 0;
-    for (uint32_t i = t; i < RANK_CELLS; i += 256) cellinfo[i] = 0;
-    __syncthreads();
-    for (uint32_t k = 2; k <= np2; k <<= 1) {
-      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-        for (uint32_t i = t; i < np2; i += 256) {
-          const uint32_t l = i ^ j;
-          if (l > i) {
-            const uint64_t a = keys[i], b = keys[l];
-            const bool up = (i & k) == 0;
-            if ((a > b) == up) { keys[i] = b; keys[l] = a; }
-          }
-        }
-        __syncthreads();
-      }
-    }
-    const uint64_t kmin = keys[0], kmax = keys[nb - 1];
-    const float dmin = key_dist(kmin);
-    float scale = (float)RANK_CELLS / (key_dist(kmax) - dmin);
-    if (!(scale < 1e30f)) scale = 0.f;             // one distinct distance (or inf/NaN): a single cell
-    // ---- the cell table: count the keys of every cell, then an exclusive scan gives the first key of each
-    for (uint32_t i = t; i < nb; i += 256) atomicAdd(&cellinfo[rank_cell(key_dist(keys[i]), dmin, scale)], 1u);
-    __syncthreads();
-    {
-      constexpr int PER = RANK_CELLS / 256;
-      uint32_t c[PER], s = 0;
-#pragma unroll
-      for (int e = 0; e < PER; ++e) { c[e] = cellinfo[t * PER + e]; s += c[e]; }
-      uint32_t tot;
-      uint32_t run = block_scan_excl(s, wsum, &tot);
-#pragma unroll
-      for (int e = 0; e < PER; ++e) { cellinfo[t * PER + e] = run | (c[e] << 16); run += c[e]; }
-    }
-    __syncthreads();
+    const RankGrid grid = rank_prepare_batch(keys, nb, hist, cellinfo, wsum);
+    const float dmin = grid.dmin, scale = grid.scale;
+    const uint64_t kmin = grid.kmin, kmax = grid.kmax;
     // ---- stream the row
     uint32_t below = 0;                            // elements before the first match: all land in hist[0]
     auto visit = [&](float d, int32_t pid, int k) {
@@ -673,16 +597,7 @@ __global__ __launch_bounds__(256) void rank_query_kernel(const float* distmat, i
     for (int k = kdone + t; k < num_g; k += 256) visit(row[k], g_pids[k], k);
     if (below) atomicAdd(&hist[0], below);
     __syncthreads();
-    // ---- inclusive prefix sums over hist in place: a contiguous odd-length span per thread (conflict-free)
-    {
-      const uint32_t per = ((hlen + 255) / 256) | 1u;
-      uint32_t s = 0;
-      for (uint32_t e = 0; e < per; ++e) s += hist[t * per + e];
-      uint32_t tot;
-      uint32_t run = block_scan_excl(s, wsum, &tot);
-      for (uint32_t e = 0; e < per; ++e) { run += hist[t * per + e]; hist[t * per + e] = run; }
-    }
-    __syncthreads();
+    rank_scan_hist(hist, grid.hlen, wsum);
     // ---- matches-before-it by chunked scans of histm; AP terms in the same order as before
     uint32_t carry_m = 0;
     double part = 0.0;
@@ -701,13 +616,7 @@ __global__ __launch_bounds__(256) void rank_query_kernel(const float* distmat, i
       }
       carry_m += tmm;
     }
-    dsum[t] = part;
-    imin[t] = fmin;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (t < o) { dsum[t] += dsum[t + o]; imin[t] = min(imin[t], imin[t + o]); }
-      __syncthreads();
-    }
+    block_tree_sum(part, fmin, dsum, imin, [](int32_t a, int32_t b) { return min(a, b); });
     ap_sum += dsum[0];
     first = min(first, imin[0]);
     nm_total += nb;
@@ -741,13 +650,7 @@ __global__ __launch_bounds__(256) void rank_finalize_kernel(const double* ap, co
       if (f < max_rank) atomicAdd(&fh[f], 1u);
     }
   }
-  dsum[t] = s;
-  nsum[t] = nv;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) { dsum[t] += dsum[t + o]; nsum[t] += nsum[t + o]; }
-    __syncthreads();
-  }
+  block_tree_sum(s, nv, dsum, nsum, [](uint32_t a, uint32_t b) { return a + b; });
   if (t == 0) {
     int64_t run = 0;
     for (int r = 0; r < max_rank; ++r) { run += fh[r]; summary[r] = run; }   // cmc = min(cumsum,1): rank.py:145-150
@@ -798,7 +701,6 @@ extern "C" int ieee_sqeuclid_distmat(const void* q, const void* g, int64_t m, in
   return launch_status("distmat");
 }
 
-static int64_t split_align(int64_t bytes) { return (bytes + 255) / 256 * 256; }
 static int split_terms(int64_t scheme) {
   return scheme == IEEE_SPLIT_BF16X3 ? 6 : (scheme == IEEE_SPLIT_BF16X2 || scheme == IEEE_SPLIT_F16X2) ? 3 : 0;
 }
@@ -806,7 +708,7 @@ static int split_terms(int64_t scheme) {
 extern "C" int64_t ieee_sqeuclid_distmat_split_workspace_bytes(int64_t m, int64_t n, int64_t d, int64_t scheme) {
   const int terms = split_terms(scheme);
   if (m <= 0 || n <= 0 || d <= 0 || terms == 0) return -1;
-  return split_align((m + n) * 8) + split_align(m * terms * d * 2) + split_align(n * terms * d * 2);
+  return align256((m + n) * 8) + align256(m * terms * d * 2) + align256(n * terms * d * 2);
 }
 
 extern "C" int ieee_sqeuclid_distmat_split(const float* q, const float* g, int64_t m, int64_t n, int64_t d,
@@ -827,8 +729,8 @@ extern "C" int ieee_sqeuclid_distmat_split(const float* q, const float* g, int64
   float* gn = qn + m;
   float* qsc = gn + n;
   float* gsc = qsc + m;
-  char* qs = (char*)work + split_align((m + n) * 8);
-  char* gs = qs + split_align(m * terms * d * 2);
+  char* qs = (char*)work + align256((m + n) * 8);
+  char* gs = qs + align256(m * terms * d * 2);
   // row norms from the fp32 rows themselves (exactly as the fp32 path)
   if (metric != 2) {
     rownorm_kernel<float><<<cdiv(m, 4), 256, 0, st>>>(q, m, (int)d, metric, qn);
@@ -887,12 +789,9 @@ static int rank_impl(const float* distmat, int64_t ldd, int64_t num_q, int64_t n
     rank_bucket_fill_kernel<<<cdiv(num_g, 256), 256, 0, st>>>(g_pids, (int)num_g, cursor, idx);
     IEEE_TRY(launch_status("rank_bucket"));
   }
-  static const int f_dbg = getenv("IEEE_RANK_DBG") ? atoi(getenv("IEEE_RANK_DBG")) : 0;    // measurement only (see the kernel)
-  if (!general_only) {
-#define IEEE_RQF(D_) rank_query_fast_kernel<D_><<<(int)num_q, 256, 0, st>>>(distmat, ldd, (int)num_g, q_pids, g_pids, q_camids, g_camids, ap, first_pos, start, idx)
-    if (f_dbg == 1) IEEE_RQF(1); else if (f_dbg == 2) IEEE_RQF(2); else if (f_dbg == 3) IEEE_RQF(3); else IEEE_RQF(0);
-#undef IEEE_RQF
-  }
+  if (!general_only)
+    rank_query_fast_kernel<<<(int)num_q, 256, 0, st>>>(distmat, ldd, (int)num_g, q_pids, g_pids, q_camids, g_camids, ap,
+                                                       first_pos, start, idx);
   rank_query_kernel<<<(int)num_q, 256, 0, st>>>(distmat, ldd, (int)num_g, q_pids, g_pids, q_camids, g_camids, ap,
                                                 first_pos, general_only ? 0 : 1);
   rank_finalize_kernel<<<1, 256, 0, st>>>(ap, first_pos, (int)num_q, (int)max_rank, summary);

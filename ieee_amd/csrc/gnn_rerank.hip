@@ -108,8 +108,6 @@ struct GnnPlan {
   int64_t N, ld, rank, s, sumsq, dwork, dwork_bytes, m0, m1, total;
 };
 
-static int64_t gnn_align(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
 static const char* gnn_plan(int64_t Q, int64_t G, int64_t d, int64_t k1, int64_t k2, int precision, GnnPlan& p) {
   if (Q <= 0 || G <= 0) return "empty query or gallery set";
   if (d <= 0 || d % 8 != 0) return "feature dim must be a positive multiple of 8";
@@ -128,7 +126,7 @@ static const char* gnn_plan(int64_t Q, int64_t G, int64_t d, int64_t k1, int64_t
                              ieee_sqeuclid_distmat_split_workspace_bytes(Q, G, p.ld, precision));
   }
   int64_t at = 0;
-  auto take = [&](int64_t bytes) { const int64_t a = at; at += gnn_align(bytes); return a; };
+  auto take = [&](int64_t bytes) { const int64_t a = at; at += align256(bytes); return a; };
   p.rank = take(N * k1 * 4);
   p.s = take(N * k1 * 4);
   p.sumsq = take(N * 4);

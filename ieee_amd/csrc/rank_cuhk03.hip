@@ -13,7 +13,7 @@
 // AP is that of the kept list (rank.py:86-90), as in the Market protocol but with the three-way filter; the ranks it
 // needs are sums of the same counts.  Nothing is sorted but the true matches, there are no atomics on floating-point
 // data, and every sum has one fixed order: two calls give the same bits.
-#include "common.h"
+#include "rank_common.h"
 
 namespace ieee {
 
@@ -25,37 +25,10 @@ constexpr int CK_UNR = 8;           // images per thread in flight while countin
 constexpr int CK_CNT = 8 * (CK_TCAP + 1);   // words of their histograms: a full batch still leaves 8 per round
 constexpr int CK_MAX_RANK = 1024;
 
-// (distance, gallery index) as one word, ascending; -0.0 == +0.0 and NaN after +inf, as ieee_rank_topk orders
-__device__ __forceinline__ uint64_t ck_key(float d, uint32_t idx) {
-  uint32_t u = __float_as_uint(d);
-  u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;
-  if (d == 0.f) u = 0x80000000u;
-  if (d != d) u = 0xFFFFFFFFu;
-  return ((uint64_t)u << 32) | idx;
-}
+static_assert(CK_THREADS == 256, "block_scan_excl and block_tree_sum are written for 256 threads");
 
-// exclusive scan of one word per thread over the 256-thread block (uses 4 LDS words)
-__device__ __forceinline__ uint32_t ck_scan_excl(uint32_t v, uint32_t* wsum, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(inc, o);
-    if (lane >= o) inc += y;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const uint32_t s = wsum[w];
-    if (w < wave) base += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
+// this protocol orders on the folded order, a stable argsort's (rank_common.h says why)
+__device__ __forceinline__ uint64_t ck_key(float d, uint32_t idx) { return order_key(order_word_folded(d), idx); }
 
 // ---- the gallery grouped by identity, once per call: sidx = gallery indices ordered on (pid, index), spid their pids.
 // The position of entry j is the number of entries before it in that order, counted against LDS tiles of the pids:
@@ -106,7 +79,7 @@ __global__ __launch_bounds__(CK_THREADS) void cuhk03_segments_kernel(const int32
     const int i = base + t;
     const uint32_t head = (i < num_g && (i == 0 || spid[i - 1] != spid[i])) ? 1u : 0u;
     uint32_t tot;
-    const uint32_t ex = ck_scan_excl(head, wsum, &tot);
+    const uint32_t ex = block_scan_excl(head, wsum, &tot);
     if (head) seg_start[carry + ex] = i;
     carry += tot;
   }
@@ -192,7 +165,7 @@ __global__ __launch_bounds__(CK_THREADS) void cuhk03_query_kernel(const float* _
         kept = g_keys[j] != qkey ? 1u : 0u;
       }
       uint32_t tot;
-      const uint32_t pos = nb + ck_scan_excl(kept, wsum, &tot);
+      const uint32_t pos = nb + block_scan_excl(kept, wsum, &tot);
       if (kept) {
         if (pos < tcap) tkeys[pos] = ck_key(row[j], (uint32_t)j);
         else if (pos == tcap) s_next = i;                          // the first one that does not fit opens the next batch
@@ -203,27 +176,11 @@ __global__ __launch_bounds__(CK_THREADS) void cuhk03_query_kernel(const float* _
       __syncthreads();
     }
     if (nb == 0) break;                                            // the rest of the segment was removed entries
-    // ---- bitonic sort of tkeys[0..np2) ascending, padded with the largest key
-    uint32_t np2 = 1;
-    while (np2 < nb) np2 <<= 1;
-    for (uint32_t i = nb + t; i < np2; i += CK_THREADS) tkeys[i] = ~0ull;
+    // ---- the batch's pmf rows and counts start over (under the sort's first barrier), the true matches are sorted
     const uint32_t nstates = nb * (uint32_t)R;
     for (uint32_t st = t; st < nstates; st += CK_THREADS) pmf[0][st] = (st % (uint32_t)R) == 0 ? 1.0 : 0.0;
     for (uint32_t i = t; i < nb; i += CK_THREADS) { others[i] = 0; before[i] = 0; }
-    __syncthreads();
-    for (uint32_t k = 2; k <= np2; k <<= 1) {
-      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-        for (uint32_t i = t; i < np2; i += CK_THREADS) {
-          const uint32_t l = i ^ j;
-          if (l > i) {
-            const uint64_t a = tkeys[i], b = tkeys[l];
-            const bool up = (i & k) == 0;
-            if ((a > b) == up) { tkeys[i] = b; tkeys[l] = a; }
-          }
-        }
-        __syncthreads();
-      }
-    }
+    lds_bitonic_sort<CK_THREADS>(tkeys, nb);
     const uint64_t kmax = tkeys[nb - 1];
     int cur = 0;
     const uint32_t stride = nb + 1;                                // words of one identity's histogram
@@ -273,13 +230,7 @@ __global__ __launch_bounds__(CK_THREADS) void cuhk03_query_kernel(const float* _
         uint32_t carry = 0;
         for (uint32_t c0 = 0; c0 < nb; c0 += 64) {
           const uint32_t i = c0 + lane;
-          uint32_t inc = i < nb ? c[i] : 0u;
-#pragma unroll
-          for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(inc, o);
-            if (lane >= o) inc += y;
-          }
-          inc += carry;
+          const uint32_t inc = wave_scan_incl(i < nb ? c[i] : 0u) + carry;
           if (i < nb) c[i] = inc;
           carry = __shfl(inc, 63);
         }
@@ -329,12 +280,7 @@ __global__ __launch_bounds__(CK_THREADS) void cuhk03_query_kernel(const float* _
     double part = 0.0;
     for (uint32_t i = t; i < nb; i += CK_THREADS)
       part += (double)(before[i] + 1u) / (double)(others[i] + before[i] + 1u);
-    col[t] = part;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if (t < o) col[t] += col[t + o];
-      __syncthreads();
-    }
+    block_tree_sum(part, col);
     ap_sum += col[0];
     nt_total += nb;
     __syncthreads();
@@ -364,13 +310,7 @@ __global__ __launch_bounds__(CK_THREADS) void cuhk03_finalize_kernel(const doubl
       s += k < max_rank ? cmc[q * max_rank + k] : a;
     }
   }
-  dsum[t] = s;
-  nsum[t] = nv;
-  __syncthreads();
-  for (int o = CK_THREADS / 2; o > 0; o >>= 1) {
-    if (t < o) { dsum[t] += dsum[t + o]; nsum[t] += nsum[t + o]; }
-    __syncthreads();
-  }
+  block_tree_sum(s, nv, dsum, nsum, [](uint32_t a, uint32_t b) { return a + b; });
   if (t == 0) {
     if (k < max_rank) {
       summary[k] = dsum[0];

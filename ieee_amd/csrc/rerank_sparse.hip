@@ -11,7 +11,7 @@
 // Every float step is the dense kernel's, in its order: the terms the dense path adds and this one skips are zeros.
 #include <algorithm>
 
-#include "common.h"
+#include "rank_common.h"
 
 namespace ieee {
 
@@ -247,23 +247,6 @@ __device__ __forceinline__ unsigned rs_load_word(const unsigned* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Exclusive scan of one value per thread over a 256-thread block; returns the block total.
-__device__ int rs_block_scan(int mine, int* s, int& excl) {
-  const int t = threadIdx.x;
-  s[t] = mine;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int add = t >= d ? s[t - d] : 0;
-    __syncthreads();
-    s[t] += add;
-    __syncthreads();
-  }
-  excl = s[t] - mine;
-  const int total = s[255];
-  __syncthreads();
-  return total;
-}
-
 // D: rows r = blockIdx.x, +gridDim.x, ...  The k2 rows are added into a dense scratch row in t order (the columns of one
 // row are distinct: no races; 0 + v = v, so skipping the dense path's zero terms keeps its bits), touched columns are
 // marked in a bitmap (global atomics), and the bitmap is walked in ascending order to emit, divide and clear.
@@ -272,7 +255,7 @@ __global__ __launch_bounds__(256) void rs_expand_kernel(const int* __restrict__ 
                                                         const float* __restrict__ Vv, int capV, int capQ,
                                                         float* __restrict__ scratch, int64_t sstride,
                                                         int* __restrict__ Qn, int* __restrict__ Qi, float* __restrict__ Qv) {
-  __shared__ int s_scan[256];
+  __shared__ uint32_t s_wsum[4];
   float* acc = scratch + (int64_t)blockIdx.x * sstride;
   unsigned* bits = (unsigned*)(acc + N);
   const int W = (N + 31) >> 5, per = (W + 255) / 256;
@@ -289,10 +272,9 @@ __global__ __launch_bounds__(256) void rs_expand_kernel(const int* __restrict__ 
       }
       __syncthreads();
     }
-    int mine = 0;
+    uint32_t mine = 0, total;
     for (int w = w0; w < w1; ++w) mine += __popc(rs_load_word(bits + w));
-    int off;
-    const int total = rs_block_scan(mine, s_scan, off);
+    int off = (int)block_scan_excl(mine, s_wsum, &total);
     for (int w = w0; w < w1; ++w) {
       unsigned b = rs_load_word(bits + w);
       if (!b) continue;
@@ -308,7 +290,7 @@ __global__ __launch_bounds__(256) void rs_expand_kernel(const int* __restrict__ 
         ++off;
       }
     }
-    if (threadIdx.x == 0) Qn[r] = min(total, capQ);
+    if (threadIdx.x == 0) Qn[r] = min((int)total, capQ);
     __syncthreads();
   }
 }
@@ -397,8 +379,6 @@ struct RsPlan {
   int64_t colmax, rank, vn, vi, vv, qn, qi, qv, cnt, off, uni, part, scr, invj, invv, total;
 };
 
-static int64_t rs_align(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
 static bool rs_plan(int64_t Q, int64_t G, int64_t k1, int64_t k2, RsPlan& p) {
   if (Q <= 0 || G <= 0 || k1 < 1 || k1 + 1 > RS_MAXK || k2 < 1 || k2 > k1 + 1) return false;
   const int64_t N = Q + G;
@@ -416,7 +396,7 @@ static bool rs_plan(int64_t Q, int64_t G, int64_t k1, int64_t k2, RsPlan& p) {
   p.P = std::min<int64_t>(N, RS_EXPAND_BLOCKS);
   p.sstride = (N + (N + 31) / 32 + 63) & ~(int64_t)63;            // floats: acc[N] + bitmap[N/32], 256-byte rows
   int64_t at = 0;
-  auto take = [&](int64_t bytes) { const int64_t a = at; at += rs_align(bytes); return a; };
+  auto take = [&](int64_t bytes) { const int64_t a = at; at += align256(bytes); return a; };
   p.colmax = take(N * 4);
   p.rank = take(N * p.K * 4);
   p.vn = take(N * 4);
@@ -430,10 +410,10 @@ static bool rs_plan(int64_t Q, int64_t G, int64_t k1, int64_t k2, RsPlan& p) {
   p.uni = at;                                      // one region, three lives: B's chunk lists, D's scratch, E's index
   const int64_t part = p.S * N * p.K * 8;
   const int64_t scr = k2 != 1 ? p.P * p.sstride * 4 : 0;
-  const int64_t inv = rs_align(G * p.capUse * 4) * 2;
+  const int64_t inv = align256(G * p.capUse * 4) * 2;
   p.part = p.scr = p.invj = p.uni;
-  p.invv = p.uni + rs_align(G * p.capUse * 4);
-  p.total = p.uni + rs_align(std::max({part, scr, inv})) + 256;
+  p.invv = p.uni + align256(G * p.capUse * 4);
+  p.total = p.uni + align256(std::max({part, scr, inv})) + 256;
   return true;
 }
 

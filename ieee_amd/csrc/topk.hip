@@ -1,8 +1,8 @@
 // Ranked retrieval: the k nearest kept gallery entries of every query, on the device.
 // Reference: torchreid/utils/reidtools.py:49 (np.argsort(distmat, axis=1)) and :110-112 (the same-identity,
 // same-camera entries are skipped); the rule is rank.py:136-137's.  The result equals a stable argsort of the
-// filtered row: order on (distance, gallery index), -0.0 == +0.0, NaN after +inf.
-#include "common.h"
+// filtered row: order on (distance, gallery index), -0.0 == +0.0, NaN after +inf (rank_common.h's folded order).
+#include "rank_common.h"
 
 namespace ieee {
 
@@ -12,16 +12,6 @@ constexpr int TOPK_UNR = 2;                                // 16-byte loads per 
 constexpr int TOPK_CHUNK = TOPK_UNR * 4 * TOPK_THREADS;    // 2048 distances streamed between two buffer checks
 constexpr int TOPK_STORE = 2 * TOPK_CHUNK;                 // LDS candidate keys (32 KB)
 constexpr int TOPK_SELECT_AT = TOPK_STORE - TOPK_CHUNK;    // more candidates than this: select down to k first
-
-// Monotone 32-bit image of a distance: equal floats (including -0.0 and +0.0) map to equal words, every NaN to the
-// largest one, so (word << 32 | index) is a total order that ties on the lower index.
-__device__ __forceinline__ uint32_t topk_word(float d) {
-  uint32_t u = __float_as_uint(d);
-  u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;
-  if (d == 0.f) u = 0x80000000u;
-  if (d != d) u = 0xFFFFFFFFu;
-  return u;
-}
 
 // One workgroup per query.  The row streams past in chunks of TOPK_CHUNK, loaded two chunks ahead; an element enters
 // the LDS candidate buffer only when its key is below the running k-th key.  When the buffer holds more than
@@ -107,9 +97,9 @@ __global__ __launch_bounds__(TOPK_THREADS) void rank_topk_kernel(const float* __
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int j = base + u * 1024 + t * 4 + e;
-        const uint32_t w = topk_word(cur[u][e]);
+        const uint32_t w = order_word_folded(cur[u][e]);
         if (j < num_g && w <= thr_hi) {
-          const uint64_t key = ((uint64_t)w << 32) | (uint32_t)j;
+          const uint64_t key = order_key(w, (uint32_t)j);
           if (key < thr) {
             const uint32_t pos = atomicAdd(&s_cnt, 1u);
             if (pos < (uint32_t)TOPK_STORE) keys[pos] = key;     // always true: a chunk fits in the room left

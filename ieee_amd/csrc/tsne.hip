@@ -274,8 +274,6 @@ struct TsnePlan {
   int64_t nslab, part, part_stride, rows, rowconst, scal, total;
 };
 
-static int64_t tsne_align(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
 static const char* tsne_plan(int64_t n, int64_t batch, TsnePlan& p) {
   if (n < 4) return "n must be at least 4";
   if (n > TSNE_MAX_N) return "n above the cap of 12288 rows";
@@ -283,7 +281,7 @@ static const char* tsne_plan(int64_t n, int64_t batch, TsnePlan& p) {
   p.nslab = (n + TSNE_SLAB - 1) / TSNE_SLAB;
   p.part_stride = p.nslab * TSNE_SUMS * n;         // floats per problem
   int64_t at = 0;
-  auto take = [&](int64_t bytes) { const int64_t a = at; at += tsne_align(bytes); return a; };
+  auto take = [&](int64_t bytes) { const int64_t a = at; at += align256(bytes); return a; };
   p.part = take(batch * p.part_stride * 4);
   p.rows = take(batch * TSNE_SUMS * n * 4);
   p.rowconst = take(batch * 2 * n * 4);

@@ -334,3 +334,46 @@ def test_rank_with_identity_buckets_equals_the_scanning_form(nq, ng, ids):
     cmc_o, map_o = ev.rank_market1501_c(d.cpu().numpy(), qp, gp, qc, gc, 20)
     nv = float(outs[1][2][20])
     assert np.array_equal(outs[1][2][:20].numpy().astype(np.float32) / np.float32(nv), cmc_o)
+
+
+def test_rank_signed_zero_order_is_the_same_on_both_paths(monkeypatch):
+    """The key order of the Market evaluator (rank_common.h, the raw order): -0.0 sorts before +0.0.  Every query has a
+    true match at -0.0 behind a non-match at +0.0 of a lower gallery index, among distances from {-0.0, +0.0, 1, inf}.
+    The oracle compares floats, for which the two zeros tie and the lower index wins, so it is not the yardstick on this
+    input; the fast and the general kernel must give the same bits, and those of the raw order restated in numpy."""
+    from ieee_amd import _lib as L
+    lib = L.require_gpu()
+    rng = np.random.RandomState(7)
+    nq, ng = 4, 1500
+    d = rng.choice(np.array([-0.0, 0.0, 1.0, np.inf], np.float32), size=(nq, ng))
+    qp, gp = np.arange(nq, dtype=np.int32), rng.randint(0, 8, ng).astype(np.int32)
+    qc, gc = np.zeros(nq, np.int32), rng.randint(0, 3, ng).astype(np.int32)
+    for i in range(nq):
+        lo, hi = 10 + 2 * i, 11 + 2 * i
+        gp[lo], d[i, lo] = nq + i, 0.0                   # a non-match at +0.0 ...
+        gp[hi], gc[hi], d[i, hi] = i, 1, -0.0            # ... and a true match at -0.0 after it in the gallery
+    assert np.signbit(d[np.arange(nq), 11 + 2 * np.arange(nq)]).all()
+    dd = torch.from_numpy(d).cuda()
+    dev = [torch.from_numpy(a).cuda() for a in (qp, gp, qc, gc)]
+    outs = []
+    for general in (False, True):
+        if general:
+            monkeypatch.setenv("IEEE_RANK_GENERAL", "1")
+        else:
+            monkeypatch.delenv("IEEE_RANK_GENERAL", raising=False)
+        ap = torch.full((nq,), 7.0, dtype=torch.float64, device="cuda")
+        first = torch.full((nq,), 7, dtype=torch.int32, device="cuda")
+        summ = torch.zeros(22, dtype=torch.int64, device="cuda")
+        L.check(lib.ieee_rank_market1501(L.ptr(dd), dd.stride(0), nq, ng, *[L.ptr(a) for a in dev], 20, L.ptr(ap),
+                                         L.ptr(first), L.ptr(summ), L.stream()))
+        torch.cuda.synchronize()
+        outs.append((ap.cpu(), first.cpu(), summ.cpu()))
+    assert all(torch.equal(a, b) for a, b in zip(*outs))
+    bits = d.view(np.uint32).astype(np.int64)
+    word = np.where(bits >> 31 != 0, bits ^ 0xFFFFFFFF, bits ^ 0x80000000)     # the raw order word
+    for i in range(nq):
+        order = np.lexsort((np.arange(ng), word[i]))
+        keep = ~((gp[order] == qp[i]) & (gc[order] == qc[i]))
+        pos = np.flatnonzero((gp[order] == qp[i])[keep])
+        assert int(outs[0][1][i]) == pos[0]
+        assert abs(float(outs[0][0][i]) - np.mean((np.arange(len(pos)) + 1.0) / (pos + 1.0))) < 1e-12
