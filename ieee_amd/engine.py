@@ -26,14 +26,16 @@ from torch.nn import functional as F
 
 from . import _lib, dist as ddp
 from .checkpoint import save_checkpoint
-from .losses import (CrossEntropyLoss, DeepSupervision, chunks_short_of_identities, multiModalMarginLossNew,
-                     target_out_of_range)
+from .losses import (CrossEntropyLoss, DeepSupervision, TripletLoss, chunks_short_of_identities,
+                     multiModalMarginLossNew, single_identity, single_identity_error, target_out_of_range,
+                     triplet_work_floats)
 from .meters import AverageMeter, DeferredSummary, MetricMeter
 from .metrics import accuracy, compute_distance_matrix, evaluate_rank
 from .optim import FUSED_OPTIMIZERS, FusedSGD
 
 _Entry = namedtuple("_Entry", "model optim sched")
 _SUMMARY_3M = ('loss', 'LossX', 'LossM', 'accR', 'lossR', 'accN', 'lossN', 'accT', 'lossT')
+_SUMMARY_3M_T = _SUMMARY_3M + ('LossT',)          # with a triplet term (Image3MEngine(weight_t > 0))
 
 
 def _hms(seconds):
@@ -462,11 +464,13 @@ def _is_native(model):
     return hasattr(model, "native_net")
 
 
-def batch_error(pids, weight_m, num_classes):
+def batch_error(pids, weight_m, num_classes, weight_t=0):
     """the exception the reference's step raises in its losses for these labels, or None (host-side: see _guard_batch)"""
     pids = pids.detach().cpu()
     if weight_m > 0 and chunks_short_of_identities(pids):
         return IndexError('tuple index out of range')
+    if weight_t > 0 and single_identity(pids):
+        return single_identity_error()               # batch-hard mining without a negative (losses.TripletLoss)
     return target_out_of_range(pids, num_classes)
 
 
@@ -476,10 +480,11 @@ class _FusedStepMixin(object):
     def _fused_ok(self):
         return _is_native(self.model) and isinstance(self.optimizer, FUSED_OPTIMIZERS) and self.use_gpu
 
-    def _guard_batch(self, pids, weight_m):
+    def _guard_batch(self, pids, weight_m, weight_t=0):
         """the reference's errors for a batch it cannot train on, raised before this step launches anything: the 3M loss's
-        IndexError when the chunks are short of identities (it runs first, margin.py:107-111), then the cross entropy's
-        RuntimeError for a label outside [0, num_classes) -- the fused step would otherwise read logits[label] out of range"""
+        IndexError when the chunks are short of identities (it runs first, margin.py:107-111), with a triplet term the
+        RuntimeError of a batch with a single identity (no negative to mine), then the cross entropy's RuntimeError for a
+        label outside [0, num_classes) -- the fused step would otherwise read logits[label] out of range"""
         # checked on every batch (64 labels: negligible next to a step); only a caller that declares its batch resident
         # (`engine.resident_batch`, bench.py: the same tensor object every step) gets the answer of the first check --
         # the address / version / shape of a DataLoader batch is NOT an identity: the allocator hands the same block out
@@ -489,12 +494,17 @@ class _FusedStepMixin(object):
         else:
             # the bound is the width of the logits the loss reads: the classifier's, as for the reference's scatter_
             classes = getattr(self.model, "num_classes", None) or self.datamanager.num_train_pids
-            err = batch_error(pids, weight_m, classes)
+            err = batch_error(pids, weight_m, classes, weight_t)
             self._guard_for, self._guard_err = (pids if self.resident_batch else None), err
         if err is not None:
             raise err
 
-    def _fused_step(self, imgs, pids, weight_x, weight_m, margin, eps, total_rows=None):
+    def _fused_step(self, imgs, pids, weight_x, weight_m, margin, eps, total_rows=None, weight_t=0, margin_t=0.3):
+        """weight_t > 0: one more launch group behind the 3M loss, ieee_triplet_hard_fwd_bwd over the three modality
+        features as ONE descriptor per row (parts = 3: nothing is concatenated), ADDING weight_t * ce-scale * its gradient
+        into df; its four numbers are appended to `small` (39 -> 43 floats, still one read-back).  Mining is within the rows
+        of this rank: under data parallelism every rank mines its own shard, as a DataParallel replica of the reference's
+        criterion would."""
         lib = _lib.require_gpu()
         m = self.model
         B, _, H, W = imgs[0].shape
@@ -527,6 +537,12 @@ class _FusedStepMixin(object):
                              torch.empty(18 * B * 2, dtype=torch.float32, device=dev),
                              torch.empty(B + 3, dtype=torch.float32, device=dev))
         dl, df, small, work, mwork = self._scratch
+        if weight_t > 0:
+            ts = getattr(self, "_scratch_t", None)
+            if ts is None or ts[1].numel() != triplet_work_floats(B) or ts[0].device != dev:
+                ts = self._scratch_t = (torch.empty(39 + 4, dtype=torch.float32, device=dev),
+                                        torch.empty(triplet_work_floats(B), dtype=torch.float32, device=dev))
+            small, twork = ts
         head_loss, head_acc, out3 = small[:18], small[18:36], small[36:39]
         ce_scale = float(weight_x) * ddp.ce_grad_scale(B, total_rows)
         _lib.check(lib.ieee_ce_ls_fwd_bwd(_lib.ptr(logits), _lib.ptr(pids), _lib.ptr(dl), _lib.ptr(head_loss),
@@ -539,7 +555,11 @@ class _FusedStepMixin(object):
         else:
             df.zero_()
             out3.zero_()
-        def guard_buffers():     # running statistics: back to the copy when the forward clamped, else the copy follows them
+        if weight_t > 0:
+            _lib.check(lib.ieee_triplet_hard_fwd_bwd(_lib.ptr(feats), 3, _lib.ptr(pids), _lib.ptr(df), _lib.ptr(small[39:43]),
+                                                     _lib.ptr(twork), B, feats.shape[2], float(margin_t),
+                                                     float(weight_t) * ddp.ce_grad_scale(B, total_rows), 1, _lib.stream()))
+        def guard_buffers():    # running statistics: back to the copy when the forward clamped, else the copy follows them
             if guard:
                 _lib.check(lib.ieee_guard_buffers(_lib.ptr(flags), _lib.ptr(m._flat_buffers), _lib.ptr(self._buf_backup),
                                                   m._flat_buffers.numel(), _lib.stream()))
@@ -695,7 +715,8 @@ class _FusedStepMixin(object):
             hl, ha = v[:18], v[18:36]
             lR, lN, lT = float(hl[0:6].sum()), float(hl[6:12].sum()), float(hl[12:18].sum())
             aR, aN, aT = float(ha[0:6].mean()), float(ha[6:12].mean()), float(ha[12:18].mean())
-            return dict(zip(keys, finish(lR, lN, lT, aR, aN, aT, float(v[36]))))
+            extra = (float(v[39]),) if v.size > 39 else ()       # a triplet term's loss rides behind the 39 numbers
+            return dict(zip(keys, finish(lR, lN, lT, aR, aN, aT, float(v[36]), *extra)))
 
         if not getattr(self, "defer_summary", False):
             return read()
@@ -767,16 +788,24 @@ class _FusedStepMixin(object):
 
 
 class Image3MEngine(_FusedStepMixin, Engine):
-    """Cross entropy over the 18 heads (label smoothed) + the 3M margin loss: engine/image/margin.py:62-154."""
+    """Cross entropy over the 18 heads (label smoothed) + the 3M margin loss: engine/image/margin.py:62-154.
+
+    weight_t > 0 adds weight_t * TripletLoss(margin_t) (batch-hard, hard_mine_triplet_loss.py) over the concatenation of
+    the three L2-normalised modality features the model returns in 'margin' mode: the softmax + triplet recipe on this
+    model, which the reference's own 'triplet' engine cannot run (it does not take IEEE3modalPart's outputs).  The
+    loss_summary then has 'LossT' and 'loss' includes the term.  The hardest positive / negative are mined among the rows
+    of ONE rank; with weight_t = 0 (the default) the step is exactly the one without the argument."""
 
     def __init__(self, datamanager, model, optimizer, margin=3, weight_m=1, weight_x=1, scheduler=None, use_gpu=True,
-                 label_smooth=True):
+                 label_smooth=True, weight_t=0, margin_t=0.3):
         super(Image3MEngine, self).__init__(datamanager, use_gpu)
         self.model, self.optimizer, self.scheduler = model, optimizer, scheduler
         self.register_model('model', model, optimizer, scheduler)
-        assert weight_m >= 0 and weight_x >= 0
+        assert weight_m >= 0 and weight_x >= 0 and weight_t >= 0
         assert weight_m + weight_x > 0
         self.weight_m, self.weight_x, self.margin = weight_m, weight_x, margin
+        self.weight_t, self.margin_t = weight_t, margin_t
+        self.criterion_t = TripletLoss(margin=margin_t)
         self.criterion_m = multiModalMarginLossNew(margin=margin)
         self.criterion_x = CrossEntropyLoss(num_classes=self.datamanager.num_train_pids, use_gpu=self.use_gpu,
                                             label_smooth=label_smooth)
@@ -785,18 +814,21 @@ class Image3MEngine(_FusedStepMixin, Engine):
         self._sync_replicas_once()
         data, total_rows = self._local_batch(data)
         imgs, pids, timeids = self.parse_data_for_train(data)
-        self._guard_batch(pids, self.weight_m)
+        self._guard_batch(pids, self.weight_m, self.weight_t)
         imgs, pids = self._to_device(imgs, pids, data.get('pid_dev') if isinstance(data, dict) else None)
         if self._fused_ok():
             small, out3 = self._fused_step(imgs, pids, self.weight_x, self.weight_m, self.margin, self.criterion_x.eps,
-                                           total_rows)
+                                           total_rows, weight_t=self.weight_t, margin_t=self.margin_t)
             loss_m = out3[0].clone()     # 'LossM' stays a 0-d device tensor like the reference's (margin.py:145)
 
-            def finish(lR, lN, lT, aR, aN, aT, lm):
+            def finish(lR, lN, lT, aR, aN, aT, lm, lt=None):
                 loss_x = lR + lN + lT
-                return (self.weight_m * lm + self.weight_x * loss_x, loss_x, loss_m, aR, lR, aN, lN, aT, lT)
+                values = (self.weight_m * lm + self.weight_x * loss_x, loss_x, loss_m, aR, lR, aN, lN, aT, lT)
+                if lt is None:
+                    return values
+                return (values[0] + self.weight_t * lt,) + values[1:] + (lt,)
 
-            return self._summary_from(small, finish, _SUMMARY_3M)
+            return self._summary_from(small, finish, _SUMMARY_3M_T if self.weight_t > 0 else _SUMMARY_3M)
         # ---- generic path: the reference's step (margin.py:102-152) over the autograd bridge
         oR, oN, oT, fR, fN, fT = self.model(imgs)
         scale = ddp.ce_grad_scale(int(pids.shape[0]), total_rows)
@@ -808,6 +840,9 @@ class Image3MEngine(_FusedStepMixin, Engine):
             per_modality = [self.compute_loss(self.criterion_x, o, pids) for o in (oR, oN, oT)]
             loss_x = per_modality[0] + per_modality[1] + per_modality[2]
             loss = loss + (self.weight_x * scale) * loss_x
+        if self.weight_t > 0:
+            loss_t = self.criterion_t(torch.cat([fR, fN, fT], 1), pids)
+            loss = loss + (self.weight_t * scale) * loss_t
         self.optimizer.zero_grad()
         loss.backward()
         self._generic_allreduce(self.model.parameters())
@@ -816,6 +851,9 @@ class Image3MEngine(_FusedStepMixin, Engine):
         shown = self.weight_m * loss_m + self.weight_x * loss_x          # the unscaled loss, as the reference logs it
         values = (float(shown), loss_x.item(), loss_m, acc[0].item(), per_modality[0].item(), acc[1].item(),
                   per_modality[1].item(), acc[2].item(), per_modality[2].item())
+        if self.weight_t > 0:
+            lt = loss_t.item()
+            return dict(zip(_SUMMARY_3M_T, (values[0] + self.weight_t * lt,) + values[1:] + (lt,)))
         return dict(zip(_SUMMARY_3M, values))
 
 

@@ -553,6 +553,38 @@ int ieee_ce_ls_fwd_bwd(const float* logits, const int64_t* targets, float* dlogi
  * out3 = {loss, label_num, chunks torch.chunk would yield}; dfeats optional; work: B+3 floats */
 int ieee_margin3m_fwd_bwd(const float* feats, const int64_t* pids, float* dfeats, float* out3, float* work,
                           int64_t B, int64_t D, float margin, float grad_scale, void* stream);
+/* Batch-hard triplet loss (torchreid/losses/hard_mine_triplet_loss.py:23-48), forward and backward, 2 launches.
+ * x [parts][B][D] fp32: the descriptor of row i is the concatenation over parts of x[p][i][0..D) (parts = 1: a plain
+ * [B][D] matrix; parts = 3: the executor's feats tensor).  d_ij = sqrt(max(d2_ij, 1e-12)) with d2 formed from DIFFERENCES,
+ * sum (x_i - x_j)^2: exactly 0 on the diagonal and for duplicate rows.  (The reference's Gram expansion in fp32 leaves
+ * +-6.6e-7 on the diagonal at D = 2304.)  Hardest positive = max over the same identity, the row itself included; hardest
+ * negative = min over the others; loss = mean over anchors of max(0, margin + d_ap - d_an).
+ * out[4] = {loss, mean d_ap, mean d_an, anchors with a positive hinge}.  dx (optional, layout of x) = the exact gradient *
+ * grad_scale, written (accumulate = 0) or added to what is there (accumulate = 1): pairs with d2 < 1e-12 contribute
+ * nothing, exactly equal maxima / minima share their anchor's gradient evenly, an anchor whose hinge is <= 0 contributes
+ * nothing.  Gather form, fixed summation order, no atomics: the same bits on every call.  Identities need not be
+ * contiguous.  A batch with one identity has no negatives: d_an = +inf, every hinge 0 (callers raise before the launch).
+ * 1 <= B <= 4096, D >= 1, 1 <= parts <= 64, else IEEE_ERR_BAD_ARG before any launch.  work: B*B + 5*B floats. */
+int ieee_triplet_hard_fwd_bwd(const float* x, int64_t parts, const int64_t* pids, float* dx, float* out, float* work,
+                              int64_t B, int64_t D, float margin, float grad_scale, int accumulate, void* stream);
+/* Per-identity-chunk centre losses, feats [M][B][D] fp32, torch.chunk semantics as ieee_margin3m_fwd_bwd has them;
+ * out3 = {loss, label_num, chunks torch.chunk would yield}; dfeats optional (written, or added to with accumulate = 1);
+ * work: B+3 floats.
+ *   mode IEEE_CENTER_HETERO (torchreid/losses/hcloss.py:18-39, M = 2), summed over the chunks:
+ *     IEEE_DIST_L2 |sum_k (c1-c2)^2|, IEEE_DIST_L1 |mean_k |c1-c2||, IEEE_DIST_COS max(0, 1 - cos(c1, c2)) (eps 1e-8);
+ *     `margin` is not used (the reference stores and ignores it).
+ *   mode IEEE_CENTER_MARGIN3M (multi_modal_margin_loss_new.py:19-40, M = 3): max(|m-d12|, |m-d23|, |m-d13|), the first
+ *     maximal argument in that order, d = IEEE_DIST_L2 (the bits of ieee_margin3m_fwd_bwd) or IEEE_DIST_L1 (nn.L1Loss:
+ *     the MEAN of absolute differences; sign(0) = 0).  IEEE_DIST_COS: IEEE_ERR_BAD_ARG (the reference's branch never
+ *     assigns its distance). */
+#define IEEE_DIST_L2 0
+#define IEEE_DIST_L1 1
+#define IEEE_DIST_COS 2
+#define IEEE_CENTER_HETERO 0
+#define IEEE_CENTER_MARGIN3M 1
+int ieee_center_pairs_fwd_bwd(const float* feats, int64_t M, const int64_t* pids, float* dfeats, float* out3,
+                              float* work, int64_t B, int64_t D, int dist_type, int mode, float margin,
+                              float grad_scale, int accumulate, void* stream);
 /* torch.optim.SGD(momentum, weight_decay, dampening=0, nesterov) as configured by the reference
  * (torchreid/optim/optimizer.py:130-138) over a flat fp32 range */
 /* The same update with two options (either may be NULL; round 6).  Reference: torchreid/optim/optimizer.py:130-138.

@@ -57,6 +57,9 @@ def main():
                     "build_transforms names): random_flip, random_crop, color_jitter, random_erase")
     ap.add_argument("--cuhk03", action="store_true", help="evaluate with the CUHK03 single-gallery-shot protocol (expected CMC "
                     "of one drawn image per gallery identity; entries of the query's identity, camera and time id removed)")
+    ap.add_argument("--weight-t", type=float, default=0.0, help="weight of a batch-hard triplet term over the concatenated "
+                    "modality features (softmax + triplet on top of the 3M loss); 0 = the reference's margin recipe")
+    ap.add_argument("--margin-t", type=float, default=0.3, help="margin of that triplet term")
     args = ap.parse_args()
 
     if args.gpus > 1 and ddp.env_world()[0] == 1:
@@ -95,7 +98,7 @@ def main():
     scheduler = build_lr_scheduler(optimizer, "multi_step", stepsize=[max(1, args.epochs * 2 // 3)], gamma=0.1)
     ranks = [r for r in (1, 5, 10, 20) if r <= len(dataset.gallery)]     # (the reference raises IndexError on a gallery of < 20)
     engine = Image3MEngine(dm, model, optimizer, margin=1, weight_m=1, weight_x=1, scheduler=scheduler, use_gpu=True,
-                           label_smooth=True)
+                           label_smooth=True, weight_t=args.weight_t, margin_t=args.margin_t)
     engine.run(save_dir=args.save_dir or os.path.join(tempfile.gettempdir(), "ieee_example_log"), max_epoch=args.epochs,
                eval_freq=args.eval_freq, print_freq=10, ranks=ranks, use_metric_cuhk03=args.cuhk03)
     mAP = engine.test(ranks=ranks, use_metric_cuhk03=args.cuhk03)           # (Engine.run does not evaluate after the last epoch, like the reference)
