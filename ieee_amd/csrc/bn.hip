@@ -1035,7 +1035,7 @@ extern "C" int ieee_bn2d_fwd(const void* y, const void* residual, void* out, int
     else bn_stats_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)y, act_gs, g, partial, partial_gs);
     IEEE_TRY(launch_status("bn_stats_kernel"));
   }
-  if (!(training && stats_rblocks < 0)) {   // stats_rblocks < 0: the producing conv finalized `stats` itself (ieee_conv2d_fwd_bn_train)
+  if (!(training && stats_rblocks < 0)) {   // stats_rblocks < 0: the caller hands in finalized `stats`: apply only
     const int lpc = training ? finalize_lpc(g.rblocks) : 32;
     bn_finalize_kernel<<<dim3(cdiv(C, 256 / lpc), (unsigned)groups), 256, 0, st>>>(
         partial, partial_gs, g.rblocks, (int)M, (int)C, gamma, beta, param_gs, running_mean, running_var, buf_gs, stats,

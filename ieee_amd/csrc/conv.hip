@@ -114,26 +114,6 @@ template <typename T> struct StoreEpi {
   }
 };
 
-// Train-mode BatchNorm finalize inside the conv that produced the sums (round 3): the workgroup that arrives LAST at a
-// column block's ticket reduces that block's per-tile partial sums (fixed tile order: deterministic) and writes the
-// unit's mean / invstd / scale / shift and running statistics, so no finalize launch sits between the conv and the
-// BatchNorm apply.  Protocol (platform guide, split-K reduction recipe): every workgroup stores its partials write-through
-// (sc1), every wave drains its stores (s_waitcnt vmcnt(0)), workgroup barrier, lane 0 takes a ticket (relaxed, agent scope);
-// the last arriver's lane 0 runs ONE agent-scope acquire, waits for it, workgroup barrier, plain loads.  Only for launches
-// of at most FIN_MAX_TILES row tiles per modality (one workgroup reads 2 x 128 x tiles partials: 64 KB at 64 tiles).
-constexpr int FIN_MAX_TILES = 64;
-struct BnFin {
-  const float* gamma = nullptr;
-  const float* beta = nullptr;
-  float* rm = nullptr;         // running mean / var (may be null)
-  float* rv = nullptr;
-  float* stats = nullptr;      // [groups][4][C]
-  int* counter = nullptr;      // [groups][tiles_n] tickets, zero before the launch; the last arriver resets its own
-  int64_t param_gs = 0, buf_gs = 0;
-  float momentum = 0.f, eps = 0.f;
-  int M = 0, on = 0;
-};
-
 // Tile epilogue through LDS: the accumulators (4 consecutive channels of one pixel per lane) are written
 // to an LDS image of the C tile, then every thread stores full 16-byte, row-contiguous chunks (a wave
 // instruction covers 4 rows x 256 B) instead of 8-byte pieces scattered over 16 rows.  Optionally adds a
@@ -169,8 +149,6 @@ template <typename T, int MODE, int VAR = 0> struct StagedStoreEpi {
   // (pwc = Wo/2 is a power of two on this path: pwl = log2; a tensor of one modality has < 2^31 elements)
   int pwc = 0, pwl = 0, pW = 0, pimg = 0, phc = 0, pnimg = 0;
   int as_wl = 0, as_hl = 0;   // VAR 2: log2 of this map's width / height (powers of two on this path)
-  BnFin fin;                  // MODE 1: finalize the BatchNorm statistics in this kernel (pointers already at this group)
-  int tn = 0;                 // column-block index (ticket slot)
   const T* by2 = nullptr;     // MODE 2: second BatchNorm input fed by the same g (BwdStats::y2) ...
   float* bn_partial2 = nullptr;   // ... and this group's [2][N][tiles_m] block for it (sum g, sum g*y2)
   long long* tot = nullptr;   // this group's [2][N] fixed-point totals (BwdStats::tot); non-null: atomics instead of bn_partial
@@ -374,7 +352,6 @@ template <typename T, int MODE, int VAR = 0> struct StagedStoreEpi {
 #pragma unroll
       for (int e = 0; e < VEC; ++e) { red[e * PLANE + t] = s1[e]; red[(VEC + e) * PLANE + t] = s2[e]; }
       __syncthreads();
-      const bool fuse = MODE == 1 && fin.on;
       for (int idx = t; idx < BN * 2; idx += 256) {
         const int q = idx / BN, c = idx % BN;          // quantity, channel within the tile
         const int cc = c / VEC, e = c % VEC;
@@ -390,8 +367,7 @@ template <typename T, int MODE, int VAR = 0> struct StagedStoreEpi {
             continue;
           }
           float* dstp = bn_partial + ((int64_t)q * N + n0 + c) * tiles_m + tile_m;
-          if (fuse) __hip_atomic_store(dstp, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // write-through (sc1)
-          else *dstp = s;
+          *dstp = s;
           if constexpr (has_y2) { if (q == 0) bn_partial2[((int64_t)n0 + c) * tiles_m + tile_m] = s; }   // sum g, for the second unit too
         }
       }
@@ -408,55 +384,6 @@ template <typename T, int MODE, int VAR = 0> struct StagedStoreEpi {
 #pragma unroll
             for (int y = 0; y < RPP; ++y) s += col[y * CPRW];
             if (n0 + c < N && tile_m < tiles_m) bn_partial2[((int64_t)N + n0 + c) * tiles_m + tile_m] = s;
-          }
-        }
-      }
-      if constexpr (MODE == 1) {
-        if (fuse) {
-          int* flag = (int*)(red + 2 * VEC * PLANE);          // one word behind the reduction planes (dynamic LDS)
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's stores (partials and output tile) have left
-          __syncthreads();
-          if (t == 0) {
-            const int ticket = __hip_atomic_fetch_add(fin.counter + tn, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = ticket == tiles_m - 1;
-          }
-          __syncthreads();
-          if (*flag) {                                          // workgroup-uniform: every other workgroup of this column is done
-            if (t == 0) {
-              __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-              __hip_atomic_store(fin.counter + tn, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-            }
-            __syncthreads();
-            double* dred = (double*)smem;                        // [2][BN] sums (the planes are consumed)
-            __syncthreads();
-            for (int idx = t; idx < BN * 2; idx += 256) {
-              const int q = idx / BN, c = idx % BN;
-              double sum = 0.0;
-              if (n0 + c < N) {
-                const float* pp = bn_partial + ((int64_t)q * N + n0 + c) * tiles_m;
-                for (int rt = 0; rt < tiles_m; ++rt) sum += (double)pp[rt];     // fixed order: the same bits whoever is last
-              }
-              dred[idx] = sum;
-            }
-            __syncthreads();
-            if (t < BN && n0 + t < N) {
-              const int c = n0 + t;
-              const double mu = dred[t] / fin.M;
-              double var = dred[BN + t] / fin.M - mu * mu;
-              if (var < 0) var = 0;
-              const float mean = (float)mu, invstd = (float)(1.0 / sqrt(var + (double)fin.eps));
-              if (fin.rm != nullptr) {
-                const double unbiased = fin.M > 1 ? var * ((double)fin.M / (double)(fin.M - 1)) : var;
-                fin.rm[c] = (1.f - fin.momentum) * fin.rm[c] + fin.momentum * mean;
-                fin.rv[c] = (1.f - fin.momentum) * fin.rv[c] + fin.momentum * (float)unbiased;
-              }
-              const float sc = fin.gamma[c] * invstd;
-              fin.stats[c] = mean;
-              fin.stats[N + c] = invstd;
-              fin.stats[2 * N + c] = sc;
-              fin.stats[3 * N + c] = fin.beta[c] - mean * sc;
-            }
           }
         }
       }
@@ -698,7 +625,6 @@ struct ConvArgs {
   int tiles_m, tiles_n;
   int group;         // m-tiles per group in the grouped tile order
   int64_t src_gs, w_gs, dst_gs;   // per-modality strides (elements)
-  int stagger = 0;   // every second workgroup of an XCD starts `stagger` x ~0.43 us late (see conv_gather_kernel)
 };
 
 // forward and dgrad share this kernel (they differ only in the gather geometry)
@@ -710,7 +636,6 @@ struct BwdStats {            // MODE 2 operands (per-group strides in elements /
   int relu;                  // MODE 3 only
   int mask_bits = 0;         // MODE 2: `mask` is the packed bit form (one byte per 8 channels)
   int addend_s2 = 0;         // MODE 2: the addend is compact at stride 2 (StagedStoreEpi VAR 2)
-  BnFin fin;                 // MODE 1: fused BatchNorm finalize (group-0 pointers; the kernels step them by blockIdx.y)
   // MODE 2, optional: a SECOND BatchNorm fed by the same gradient g (the downsample branch of the block whose output this
   // dgrad differentiates): y2 = its input tensor (same shape and strides as y), partial2 = its own [2][N][tiles_m] block per
   // group, which receives sum g (again) and sum g*y2 -- that unit's ieee_bn2d_bwd then skips its reduction pass too
@@ -724,35 +649,15 @@ struct BwdStats {            // MODE 2 operands (per-group strides in elements /
   float tot_lim = TOT_RANGE;    //             a tile's share of the range: 2^62 / row tiles of the launch
 };
 
-// MODE 1: hand the epilogue its group's finalize operands
-template <class Epi> __device__ __forceinline__ void set_fin(Epi& epi, const BwdStats& bs, int z, int tn, int tiles_n, int N) {
-  if (!bs.fin.on) return;
-  epi.fin = bs.fin;
-  epi.fin.gamma += z * bs.fin.param_gs;
-  epi.fin.beta += z * bs.fin.param_gs;
-  if (bs.fin.rm != nullptr) { epi.fin.rm += z * bs.fin.buf_gs; epi.fin.rv += z * bs.fin.buf_gs; }
-  epi.fin.stats += (int64_t)z * 4 * N;
-  epi.fin.counter += z * tiles_n;
-  epi.tn = tn;
-}
-
 // (forcing 4 waves per SIMD here spills 80 VGPRs and is 2.5x slower; the default allocation gives 3)
 // PIPE = 0: register staging, one LDS stage (high occupancy: the many-workgroup layers).  PIPE = 2..4: LDS-DMA ring
 // of PIPE stages with PIPE-1 k-tiles in flight (few-workgroup layers, where no co-resident workgroup hides the
 // load latency of a one-tile-deep pipeline); bf16 fast path only.
 template <typename T, int BN, bool SLOW, int MODE, int PIPE = 0, int VAR = 0>
-__global__ __launch_bounds__(256, (BN == 256 ? 2 : (PIPE == 1 ? 4 : ((PIPE == 5 || PIPE == 6) ? 3 : 1)))) void conv_gather_kernel(const T* __restrict__ src, const T* __restrict__ w,
+__global__ __launch_bounds__(256, (BN == 256 ? 2 : (PIPE == 1 ? 4 : (PIPE == 5 ? 3 : 1)))) void conv_gather_kernel(const T* __restrict__ src, const T* __restrict__ w,
                                                           T* __restrict__ dst, const T* __restrict__ addend,
                                                           float* __restrict__ bn_partial, ConvArgs a, BwdStats bs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // Phase stagger (round 6, IEEE_GATHER_STAGGER): a launch of one or two rounds of identical workgroups runs in LOCKSTEP --
-  // every workgroup of the chip is in its k-loop (L2 -> LDS path saturated, HBM store path idle), then every workgroup is in
-  // its epilogue (the reverse): the measurement build without epilogues shows 15-60 % of such a launch is epilogue time that
-  // nothing overlaps.  Every second workgroup of an XCD therefore starts a fraction of a tile late, so that the two halves
-  // of the co-resident workgroups sit in opposite phases.
-  if (a.stagger > 0 && ((blockIdx.x >> 3) & 1)) {
-    for (int i = 0; i < a.stagger; ++i) __builtin_amdgcn_s_sleep(16);
-  }
   int tm, tn;
   tile_map_xy(a.tiles_m, a.tiles_n, a.group, tm, tn);
   const int m0 = tm * 128, n0 = tn * BN;
@@ -767,7 +672,6 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : (PIPE == 1 ? 4 : ((PIPE == 5 
                               (MODE == 2 && bs.mask && !bs.mask_bits) ? (const T*)bs.mask + z * bs.act_gs : nullptr,
                               ((MODE == 2 || MODE == 3) && bs.stats) ? bs.stats + z * bs.stats_gs : nullptr};
   if constexpr (MODE == 3) epi.relu = bs.relu;
-  if constexpr (MODE == 1) set_fin(epi, bs, z, tn, a.tiles_n, a.N);
   if constexpr (MODE == 1 || MODE == 2) {
     if (bs.tot != nullptr) { epi.tot = bs.tot + z * bs.tot_gs + (tm & (bs.tot_rep - 1)) * bs.tot_rs; epi.tot_flag = bs.tot_flag; epi.tot_lim = bs.tot_lim; }
   }
@@ -864,7 +768,6 @@ __global__ __launch_bounds__(256, 3) void conv3x3_patch_kernel(const bf16* __res
                                     (MODE == 2 && bs.mask && !bs.mask_bits) ? (const bf16*)bs.mask + z * bs.act_gs : nullptr,
                                     ((MODE == 2 || MODE == 3) && bs.stats) ? bs.stats + z * bs.stats_gs : nullptr};
   if constexpr (MODE == 3) epi.relu = bs.relu;
-  if constexpr (MODE == 1) set_fin(epi, bs, z, tn, a.tiles_n, a.N);
   if constexpr (MODE == 1 || MODE == 2) {
     if (bs.tot != nullptr) { epi.tot = bs.tot + z * bs.tot_gs + (tm & (bs.tot_rep - 1)) * bs.tot_rs; epi.tot_flag = bs.tot_flag; epi.tot_lim = bs.tot_lim; }
   }
@@ -1083,18 +986,15 @@ static bool patch_eligible(const GatherGeom& g, int M) {
 // contiguous 256-byte run per 16 lanes: conflict-free with no swizzle and no address arithmetic in the loop.  The packed
 // weights (64 x 256 bf16 = 32 KB) never enter LDS: each wave keeps its B fragments of all 8 k-steps in registers.
 // No barrier inside the k-loop.  Same staged epilogue (BatchNorm sums / folded eval BatchNorm) as the GEMM kernel.
-// WALK > 1 (round 6): the workgroup is persistent over WALK consecutive tiles (2 * WALK output rows of one image).  The 32 KB of
-// packed weights -- 64 KB of L2 -> register traffic per workgroup, six times the 10.7 KB patch -- are fetched ONCE instead of
-// once per two output rows, and the next tile's patch lands (second patch region) under this tile's MFMAs and staged epilogue.
-// LDS: epilogue staging 18 KB + 2 x 11 KB = 40 KB: still 4 workgroups per CU.
-constexpr int STEM_EPI_BYTES = 128 * (64 * 2 + 16), STEM_PATCH_BYTES = 11 * 1024;
-template <int MODE, int WALK = 1>
+// The patch shares the epilogue's staging region: it is consumed before the epilogue stages.
+constexpr int STEM_EPI_BYTES = 128 * (64 * 2 + 16);
+template <int MODE>
 __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const bf16* __restrict__ src, const bf16* __restrict__ w,
                                                            bf16* __restrict__ dst, float* __restrict__ bn_partial,
                                                            ConvArgs a, BwdStats bs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  int tg, tn;
-  tile_map_xy(a.tiles_m / WALK, 1, a.group, tg, tn);
+  int tm, tn;
+  tile_map_xy(a.tiles_m, 1, a.group, tm, tn);
   const int z = blockIdx.y;
   src += z * a.src_gs;
   w += z * a.w_gs;
@@ -1105,9 +1005,8 @@ __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const bf16* __restric
   const int rowb = Wp * 8;                                   // bytes per input row (4 bf16 channels per pixel)
   const int patch_bytes = 10 * rowb;
   const int ninstr = (patch_bytes + 1023) >> 10;
-  // WALK == 1: the patch shares the staging region (it is consumed before the epilogue stages); else two regions behind it
-  auto patch_at = [&](int rep) -> char* { return WALK == 1 ? smem : smem + STEM_EPI_BYTES + (rep & 1) * STEM_PATCH_BYTES; };
-  auto fetch_patch = [&](int tm, char* dstp) {
+  const char* patch = smem;
+  {
     const int img = tm / tiles_per_img, oh0 = (tm - img * tiles_per_img) * 2;
     const char* pbase = (const char*)src + ((int64_t)(img * Hp + 2 * oh0) * Wp) * 8;
 #pragma unroll
@@ -1115,11 +1014,10 @@ __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const bf16* __restric
       const int j = wave_u + 4 * k;
       if (j < ninstr) {
         const unsigned off = (unsigned)min(j * 1024 + lane * 16, patch_bytes - 16);   // the tail lanes re-read the last chunk
-        glds16_s(off, pbase, dstp + j * 1024);
+        glds16_s(off, pbase, smem + j * 1024);
       }
     }
-  };
-  fetch_patch(tg * WALK, patch_at(0));
+  }
   // B fragments of all 8 k-steps: lane (n = lane & 15, k-chunk lane >> 4) of n-fragment j
   bf16x8 fb[8][2];
 #pragma unroll
@@ -1128,33 +1026,27 @@ __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const bf16* __restric
     for (int j = 0; j < 2; ++j)
       fb[ks][j] = __builtin_bit_cast(bf16x8, *(const uint4*)(w + (int64_t)(wn * 32 + j * 16 + (lane & 15)) * a.ldw + ks * 32 + (lane >> 4) * 8));
   const unsigned abase = (unsigned)(2 * wm * rowb + (lane & 15) * 16 + (lane >> 4) * 16);
-#pragma unroll 1
-  for (int rep = 0; rep < WALK; ++rep) {
-    const int tm = tg * WALK + rep;
-    StagedStoreEpi<bf16, MODE, 0> epi{0, dst, nullptr, MODE == 1 ? bn_partial + (int64_t)z * a.tiles_m * 2 * a.N : nullptr, a.N, a.M, a.N, tm, a.tiles_m,
-                                      nullptr, nullptr, (MODE == 3 && bs.stats) ? bs.stats + z * bs.stats_gs : nullptr};
-    if constexpr (MODE == 3) epi.relu = bs.relu;
-    f32x4 acc[4][2];
+  StagedStoreEpi<bf16, MODE, 0> epi{0, dst, nullptr, MODE == 1 ? bn_partial + (int64_t)z * a.tiles_m * 2 * a.N : nullptr, a.N, a.M, a.N, tm, a.tiles_m,
+                                    nullptr, nullptr, (MODE == 3 && bs.stats) ? bs.stats + z * bs.stats_gs : nullptr};
+  if constexpr (MODE == 3) epi.relu = bs.relu;
+  f32x4 acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  wait_vmcnt<0>();                      // the patch has landed ...
+  __syncthreads();                      // ... for every wave
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) {
+    bf16x8 fa[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) fa[i] = __builtin_bit_cast(bf16x8, *(const uint4*)(patch + abase + ks * rowb + i * 256));
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    wait_vmcnt<0>();                      // this tile's patch has landed (and the previous tile's stores have left)
-    __syncthreads();                      // ... for every wave; the other patch region was last read a tile ago
-    if (WALK > 1 && rep + 1 < WALK) fetch_patch(tm + 1, patch_at(rep + 1));
-    const char* patch = patch_at(rep);
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      bf16x8 fa[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[i] = __builtin_bit_cast(bf16x8, *(const uint4*)(patch + abase + ks * rowb + i * 256));
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(fb[ks][j], fa[i], acc[i][j]);
-    }
-    epi.template finish<128, 64, 4, 2>(acc, smem, tm * 128, 0);
+      for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(fb[ks][j], fa[i], acc[i][j]);
   }
+  epi.template finish<128, 64, 4, 2>(acc, smem, tm * 128, 0);
 }
 
 // the shapes the direct stem covers: 8x8 / stride 2 / no padding over 4 channels, 64 output channels, 64 output columns
@@ -1292,35 +1184,6 @@ static int64_t stem_wgrad_splits(int dtype, int64_t N, int64_t Hi, int64_t Wi, i
 }
 
 
-// ------------------------------------------------------------------ the PREVIOUS weight gradient's slab reduction as this launch's prologue
-// (round 6) 53 wgrad_reduce launches of 10-30 us sat between the weight-gradient GEMMs of the side stream.  A reduction
-// folded into the tail of its own GEMM launch (SlabFoldEpi above) needs one reducer per output tile -- measured +0.68 ms per
-// step: a single workgroup has ~32 KB of loads in flight and reads its 0.5 MB of slabs at ~20 GB/s while the chip idles.
-// Folded into the HEAD of the NEXT weight-gradient launch instead, every workgroup of that launch takes a share
-// (blocks bx, bx + grid, ... of the reduction's own grid), the kernel boundary in between is the only synchronisation
-// (no tickets, no fences, plain stores), the arithmetic is wgrad_reduce_body / wgrad_reduce_taps_body unchanged -- the
-// same bits as the reduction launch -- and the slabs are read while they are still cache-resident.  The caller alternates
-// between two slab regions and flushes the last pending reduction of a group of layers with ieee_wgrad_reduce_pending.
-template <int VEC>
-__device__ __forceinline__ void wgrad_reduce_body(float* part, int bx, int z, const float* __restrict__ slab, float* __restrict__ dw,
-                                                  int splitk, int Co, int Ci, int RS, int64_t slab_gs, int64_t dw_gs,
-                                                  int accumulate, int sl_log2);
-__device__ __forceinline__ void wgrad_reduce_taps_body(float* tile, int bx, int z, const float* __restrict__ slab,
-                                                       float* __restrict__ dw, int splitk, int Co, int Ci, int RS, int64_t slab_gs,
-                                                       int64_t dw_gs, int accumulate);
-__device__ __forceinline__ void wgrad_prologue(const ieee_wgrad_reduce_desc& d, int groups, char* smem) {
-  if (d.kind == 0) return;
-  float* lds = (float*)smem;                 // >= 256 * 4 floats (split-lane forms) / [128][9] floats (taps form): < 5 KB
-  const int total = d.blocks * groups;
-  for (int w = blockIdx.x; w < total; w += gridDim.x) {
-    const int z = w / d.blocks, bx = w - z * d.blocks;
-    if (d.kind == 1) wgrad_reduce_body<4>(lds, bx, z, d.slab, d.dw, d.nsplit, d.Co, d.Ci, d.RS, d.slab_gs, d.dw_gs, d.accumulate, d.sl_log2);
-    else if (d.kind == 2) wgrad_reduce_body<1>(lds, bx, z, d.slab, d.dw, d.nsplit, d.Co, d.Ci, d.RS, d.slab_gs, d.dw_gs, d.accumulate, d.sl_log2);
-    else wgrad_reduce_taps_body(lds, bx, z, d.slab, d.dw, d.nsplit, d.Co, d.Ci, d.RS, d.slab_gs, d.dw_gs, d.accumulate);
-    __syncthreads();                         // the staging floats are reused by the next share / the GEMM's operand stage
-  }
-}
-
 // ------------------------------------------------------------------ 3x3 / stride 1 weight gradient over LDS patches
 // dW[co][(r, s, ci)] = sum over pixels of dY[pix][co] * X[pix + (r - 1, s - 1)][ci].  The TN kernel above treats the 9 taps as 9
 // independent column blocks: X is fetched from L2 once per tap and dY once per 128 columns.  Here a workgroup owns
@@ -1353,14 +1216,12 @@ struct WgradPatchArgs {
 
 template <int WLOG, bool HALF_M, bool FOLD = false>
 __global__ __launch_bounds__(256, 3) void conv3x3_wgrad_patch_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x,
-                                                                     float* slab, WgradPatchArgs a, FoldArgs fa,
-                                                                     ieee_wgrad_reduce_desc prev) {
+                                                                     float* slab, WgradPatchArgs a, FoldArgs fa) {
   typedef WPatch<WLOG> WP;
   typedef ImgTN<bf16> Img;
   typedef s16x4 __attribute__((address_space(3))) * lds_s16x4;
   typedef __attribute__((ext_vector_type(8))) short s16x8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  wgrad_prologue(prev, a.groups, smem);
   // every tile of one (k-split, modality) goes to ONE XCD (blocks b, b + 8, ... share an L2): they read the same pixels
   const int bid = blockIdx.x, xcd = bid & 7, jb = bid >> 3;
   const int kzi = (jb / a.tiles) * 8 + xcd;
@@ -1514,9 +1375,8 @@ struct WgradArgs {
 #endif
 template <typename T, bool SLOW, int PIPE, bool HALF_M, class Epi>
 __device__ __forceinline__ void conv_wgrad_body(const T* __restrict__ dy, const T* __restrict__ x, float* slab, const WgradArgs& a,
-                                                const FoldArgs* fa, const ieee_wgrad_reduce_desc& prev) {
+                                                const FoldArgs* fa) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  wgrad_prologue(prev, a.groups, smem);
   // XCD-aware order: every tile of one (k-split, modality) reads the same pixel range of dY and X, so all of
   // them go to ONE XCD (blocks b, b+8, ... share an XCD/L2) and that range is fetched into one L2 only.
   int kzi, tile;
@@ -1604,16 +1464,15 @@ __device__ __forceinline__ void conv_wgrad_body(const T* __restrict__ dy, const 
 
 template <typename T, bool SLOW, int PIPE = 0, bool HALF_M = false>
 __global__ __launch_bounds__(256, (PIPE == 1 ? IEEE_WGRAD_OCC : 3)) void conv_wgrad_kernel(const T* __restrict__ dy, const T* __restrict__ x,
-                                                         float* __restrict__ slab, WgradArgs a, ieee_wgrad_reduce_desc prev) {
-  conv_wgrad_body<T, SLOW, PIPE, HALF_M, SlabEpi>(dy, x, slab, a, nullptr, prev);
+                                                         float* __restrict__ slab, WgradArgs a) {
+  conv_wgrad_body<T, SLOW, PIPE, HALF_M, SlabEpi>(dy, x, slab, a, nullptr);
 }
 // the same GEMM with the split-K fold inside the launch (FoldArgs, SlabFoldEpi); bf16 LDS-DMA path only.  `slab` is not
 // __restrict__ / const here: other workgroups' stores to it are read back behind the acquire.
 template <bool HALF_M>
 __global__ __launch_bounds__(256, IEEE_WGRAD_OCC) void conv_wgrad_fold_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x,
-                                                                              float* slab, WgradArgs a, FoldArgs fa,
-                                                                              ieee_wgrad_reduce_desc prev) {
-  conv_wgrad_body<bf16, false, 1, HALF_M, SlabFoldEpi>(dy, x, slab, a, &fa, prev);
+                                                                              float* slab, WgradArgs a, FoldArgs fa) {
+  conv_wgrad_body<bf16, false, 1, HALF_M, SlabFoldEpi>(dy, x, slab, a, &fa);
 }
 
 // dW[z][co][ci][r][s] (OIHW fp32, the reference's parameter layout) = sum over splits of
@@ -1646,7 +1505,7 @@ __device__ __forceinline__ void wgrad_reduce_body(float* part, int bx, int z, co
       }
     }
   }
-  // (no early return: the body also runs as the prologue of the NEXT weight-gradient launch, wgrad_prologue)
+  // (no early return above: every thread reaches the barrier below)
   if (SL > 1) {
 #pragma unroll
     for (int e = 0; e < VEC; ++e) part[(lane * per + x) * VEC + e] = acc[e];
@@ -2004,10 +1863,6 @@ static GatherPlan plan_gather(int M, int N, int ktiles, int groups) {
     if (f_narrow == 1) p.bn = 64;
     if (f_pipe >= 0) p.pipe = f_pipe;
   }
-  // IEEE_GATHER_DUAL (default 0 until measured; gemm_nt_dma, DMA_STAGES == 6): two k-tiles per round trip for the 128 x 64
-  // launches that cannot offer more than 3 workgroups per CU and have a long enough K
-  static const int f_dual = getenv("IEEE_GATHER_DUAL") ? atoi(getenv("IEEE_GATHER_DUAL")) : 0;
-  if (f_dual > 0 && p.bn == 64 && N > 64 && p.pipe == 1 && ktiles >= f_dual && (int64_t)cdiv(M, 128) * cdiv(N, 64) * groups <= 768) p.pipe = 6;
   if (p.bn == 256 && p.pipe != 1) p.pipe = 0;
   if (ktiles < 2 && p.pipe > 1) p.pipe = 0;
   return p;
@@ -2016,8 +1871,7 @@ static GatherPlan plan_gather(int M, int N, int ktiles, int groups) {
 template <typename T>
 static int launch_gather(const T* src, const T* w, T* dst, const T* addend, const GatherGeom& g, int M, int N,
                          int Ktrue, int ldw, int groups, int64_t src_gs, int64_t w_gs, int64_t dst_gs, bool slow,
-                         hipStream_t st, float* bn_partial = nullptr, const BwdStats* bwd = nullptr, bool affine = false,
-                         const BnFin* fin = nullptr) {
+                         hipStream_t st, float* bn_partial = nullptr, const BwdStats* bwd = nullptr, bool affine = false) {
   const int BK = ImgNT<T>::BK;
   ConvArgs a;
   a.g = g;
@@ -2033,16 +1887,10 @@ static int launch_gather(const T* src, const T* w, T* dst, const T* addend, cons
   GatherPlan plan{N <= 64 ? 64 : 128, 0};
   if (sizeof(T) == 2 && !slow) plan = plan_gather(M, N, a.ktiles, groups);
   const bool narrow = plan.bn == 64;
-  if (plan.pipe == 6 && (a.g.perm || (bwd && (bwd->addend_s2 || bwd->y2)))) plan.pipe = 1;   // (forms with epilogue variants of their own)
   if (plan.pipe != 1 || plan.bn == 256 || affine || (bn_partial && !bwd)) a.g.perm = 0;   // class-major rows: default pipeline, dgrad modes
   a.tiles_n = cdiv(N, plan.bn);
   dim3 grid(a.tiles_m * a.tiles_n, groups);
-  {   // phase stagger: launches of at most IEEE_GATHER_STAGGER_MAXWG workgroups (default 3072: at most 3 rounds at 4 per CU)
-    static const int f_stag = getenv("IEEE_GATHER_STAGGER") ? atoi(getenv("IEEE_GATHER_STAGGER")) : 0;
-    static const int64_t f_stag_wg = getenv("IEEE_GATHER_STAGGER_MAXWG") ? atoll(getenv("IEEE_GATHER_STAGGER_MAXWG")) : 3072;
-    a.stagger = ((int64_t)grid.x * groups <= f_stag_wg) ? f_stag : 0;
-  }
-  const int stages = plan.pipe == 5 ? 1 : (plan.pipe == 6 ? 2 : (plan.pipe ? plan.pipe : (sizeof(T) == 2 ? 1 : 2)));   // PIPE 5 = one stage too, 6 = two
+  const int stages = plan.pipe == 5 ? 1 : (plan.pipe ? plan.pipe : (sizeof(T) == 2 ? 1 : 2));   // PIPE 5 = one stage too
   size_t smem = (size_t)stages * (128 + plan.bn) * 128;
   {   // the LDS-staged epilogue needs the C tile: bf16 rows padded by 16 B, fp32 rows unpadded
     const size_t bn = plan.bn;
@@ -2072,21 +1920,13 @@ static int launch_gather(const T* src, const T* w, T* dst, const T* addend, cons
   BwdStats bs{nullptr, nullptr, nullptr, 0, 0, 0};
   if (bwd) bs = *bwd;
   if (tl_totals != nullptr) {      // armed by ieee_conv_next_bn_totals for this launch
-    if (stats && bs.y2 == nullptr && !(fin != nullptr && fin->on)) {
+    if (stats && bs.y2 == nullptr) {
       bs.tot = tl_totals; bs.tot_gs = tl_totals_gs; bs.tot_rep = tl_totals_rep; bs.tot_rs = tl_totals_gs * groups;
       bs.tot_flag = tl_totals_flag != nullptr ? tl_totals_flag + (bwd ? 1 : 0) : nullptr;
       bs.tot_lim = nextafterf(TOT_RANGE / (float)cdiv(M, 128), 0.f);   // (rounded DOWN: tiles * lim <= 2^62 exactly)
     }
     tl_totals = nullptr;
     tl_totals_flag = nullptr;
-  }
-  if (fin != nullptr && fin->on) {
-    if (!(sizeof(T) == 2 && !slow && stats && !bwd && !affine && cdiv(M, 128) <= FIN_MAX_TILES && a.g.Cs != 4)) {
-      set_error(IEEE_ERR_UNSUPPORTED, "conv: the fused BatchNorm finalize needs the bf16 training form with at most %d row tiles", FIN_MAX_TILES);
-      return IEEE_ERR_UNSUPPORTED;
-    }
-    bs.fin = *fin;
-    bs.fin.M = M;
   }
   if (affine && slow) {
     set_error(IEEE_ERR_UNSUPPORTED, "conv: the fused inference BatchNorm needs the vector path");
@@ -2105,18 +1945,11 @@ static int launch_gather(const T* src, const T* w, T* dst, const T* addend, cons
   }
   if constexpr (sizeof(T) == 2) {
     if (!slow && stem_eligible(a.g, N, ldw, mode, addend)) {
-      // IEEE_STEM_WALK=4 (default 1): tiles per persistent workgroup -- the training forms only (mode 0 / 1).  Built and measured
-      // in round 6 (LABNOTES R6.3c): the launch itself got SLOWER inside the step (128.7 -> 161.8 us in a trace pair: 3 072
-      // four-tile chains at 40 KB of LDS instead of 12 288 short workgroups that hide each other's patch and weight latency),
-      // the step moved by -0.02 ms (median of 6 interleaved rounds, inside the noise).  Kept as an option.
-      static const int f_walk = getenv("IEEE_STEM_WALK") ? atoi(getenv("IEEE_STEM_WALK")) : 1;
-      const bool walk = f_walk == 4 && mode != 3 && a.tiles_m % 4 == 0 && (a.g.Ho >> 1) % 4 == 0;
-      dim3 sgrid(walk ? a.tiles_m / 4 : a.tiles_m, groups);
-      const size_t ssm = walk ? STEM_EPI_BYTES + 2 * STEM_PATCH_BYTES : STEM_EPI_BYTES;   // staged epilogue (18 KB) > patch (11 KB) > BN-sum scratch
+      // (a workgroup persistent over four tiles was measured in round 6 and lost: LABNOTES R6.3c)
+      dim3 sgrid(a.tiles_m, groups);
+      const size_t ssm = STEM_EPI_BYTES;   // staged epilogue (18 KB) > patch (11 KB) > BN-sum scratch
       if (mode == 3) launch_timed(stem_conv_kernel<3>, sgrid, ssm, st, src, w, dst, (float*)nullptr, a, bs);
-      else if (mode == 1 && walk) launch_timed(stem_conv_kernel<1, 4>, sgrid, ssm, st, src, w, dst, bn_partial, a, bs);
       else if (mode == 1) launch_timed(stem_conv_kernel<1>, sgrid, ssm, st, src, w, dst, bn_partial, a, bs);
-      else if (walk) launch_timed(stem_conv_kernel<0, 4>, sgrid, ssm, st, src, w, dst, (float*)nullptr, a, bs);
       else launch_timed(stem_conv_kernel<0>, sgrid, ssm, st, src, w, dst, (float*)nullptr, a, bs);
       return launch_status("stem_conv_kernel");
     }
@@ -2156,7 +1989,6 @@ static int launch_gather(const T* src, const T* w, T* dst, const T* addend, cons
         case 2: IEEE_GATHER_CASE(64, 2); break;
         case 3: IEEE_GATHER_CASE(64, 3); break;
         case 4: IEEE_GATHER_CASE(64, 4); break;
-        case 6: IEEE_GATHER_CASE(64, 6); break;
         default: IEEE_GATHER_CASE(64, 0); break;
       }
     } else {
@@ -2302,31 +2134,6 @@ extern "C" int ieee_conv2d_fwd(const void* x, const void* w_packed, void* y, int
     return launch_gather<bf16>((const bf16*)x, (const bf16*)w_packed, (bf16*)y, nullptr, g, g.npix, d.Co,
                                d.R * d.S * d.Ci, ldw, (int)groups, x_gs, w_gs, y_gs, slow, st, bn_partial);
   IEEE_REQUIRE(false, "conv2d_fwd: bad dtype %d", dtype);
-}
-
-extern "C" int64_t ieee_conv2d_fwd_bn_train_max_rows(void) { return (int64_t)FIN_MAX_TILES * 128; }
-
-extern "C" int ieee_conv2d_fwd_bn_train(const void* x, const void* w_packed, void* y, int dtype, int64_t groups, int64_t N,
-                                        int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co, int64_t R, int64_t S, int64_t stride,
-                                        int64_t pad, int64_t x_gs, int64_t w_gs, int64_t y_gs, float* bn_partial,
-                                        const float* gamma, const float* beta, int64_t param_gs, float* running_mean,
-                                        float* running_var, int64_t buf_gs, float* stats, float momentum, float eps,
-                                        int32_t* tickets, void* stream) {
-  ieee::OneShotArms disarm;
-  IEEE_REQUIRE(x && w_packed && y && bn_partial && gamma && beta && stats && tickets, "conv2d_fwd_bn_train: null pointer");
-  IEEE_REQUIRE(dtype == IEEE_BF16, "conv2d_fwd_bn_train: bf16 only");
-  Dims d;
-  IEEE_TRY(check_dims("conv2d_fwd_bn_train", N, Hi, Wi, Ci, Co, R, S, stride, pad, &d));
-  IEEE_REQUIRE(Co % 8 == 0 && Ci % 64 == 0, "conv2d_fwd_bn_train: Cin %% 64, Cout %% 8");
-  IEEE_REQUIRE((int64_t)d.N * d.Ho * d.Wo <= ieee_conv2d_fwd_bn_train_max_rows(), "conv2d_fwd_bn_train: more than %ld output pixels",
-               (long)ieee_conv2d_fwd_bn_train_max_rows());
-  GatherGeom g{d.Hi, d.Wi, d.Ci, d.Ho, d.Wo, d.R, d.S, d.stride, -d.pad, +1, 1, d.N * d.Ho * d.Wo};
-  const int ldw = (int)ieee_conv_packed_ld(dtype, Ci, R, S);
-  BnFin fin;
-  fin.gamma = gamma; fin.beta = beta; fin.rm = running_mean; fin.rv = running_var; fin.stats = stats; fin.counter = (int*)tickets;
-  fin.param_gs = param_gs; fin.buf_gs = buf_gs; fin.momentum = momentum; fin.eps = eps; fin.on = 1;
-  return launch_gather<bf16>((const bf16*)x, (const bf16*)w_packed, (bf16*)y, nullptr, g, g.npix, d.Co, d.R * d.S * d.Ci, ldw,
-                             (int)groups, x_gs, w_gs, y_gs, false, (hipStream_t)stream, bn_partial, nullptr, false, &fin);
 }
 
 extern "C" int ieee_conv2d_fwd_bn_eval(const void* x, const void* w_packed, void* out, const void* residual,
@@ -2483,40 +2290,18 @@ static void fill_reduce_desc(ieee_wgrad_reduce_desc* o, const float* slab, float
   o->kind = kind; o->sl_log2 = sl_log2; o->blocks = blocks; o->accumulate = accumulate; o->block_begin = 0; o->reserved_ = 0;
 }
 
-// one described reduction as a launch of its own (the immediate path's kernels and grids)
-static int reduce_launch(const ieee_wgrad_reduce_desc& d, int64_t groups, hipStream_t st) {
-  if (d.kind == 0) return IEEE_OK;
-  dim3 grid((unsigned)d.blocks, (unsigned)groups);
-  if (d.kind == 3) {
-    wgrad_reduce_taps_kernel<<<grid, 256, (size_t)RT_CIB * d.RS * sizeof(float), st>>>(d.slab, d.dw, d.nsplit, d.Co, d.Ci, d.RS, d.slab_gs,
-                                                                                      d.dw_gs, d.accumulate);
-    return launch_status("wgrad_reduce_taps_kernel");
-  }
-  if (d.kind == 1)
-    wgrad_reduce_kernel<4><<<grid, 256, 0, st>>>(d.slab, d.dw, d.nsplit, d.Co, d.Ci, d.RS, d.slab_gs, d.dw_gs, d.accumulate, d.sl_log2);
-  else
-    wgrad_reduce_kernel<1><<<grid, 256, 0, st>>>(d.slab, d.dw, d.nsplit, d.Co, d.Ci, d.RS, d.slab_gs, d.dw_gs, d.accumulate, d.sl_log2);
-  return launch_status("wgrad_reduce_kernel");
-}
-
 // defer != NULL: run the GEMM only and describe the slab reduction in *defer (kind 0: nothing left to do)
 static int wgrad_impl(const void* dy, const void* x, float* dw_oihw, void* work, int dtype, int64_t groups,
                       int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co, int64_t R, int64_t S,
                       int64_t stride, int64_t pad, int64_t dy_gs, int64_t x_gs, int64_t dw_gs,
-                      int accumulate, void* stream, ieee_wgrad_reduce_desc* defer, int32_t* tickets = nullptr,
-                      const ieee_wgrad_reduce_desc* prev = nullptr) {
+                      int accumulate, void* stream, ieee_wgrad_reduce_desc* defer, int32_t* tickets = nullptr) {
   IEEE_REQUIRE(dy && x && dw_oihw && work, "conv2d_wgrad: null pointer");
   Dims d;
   IEEE_TRY(check_dims("conv2d_wgrad", N, Hi, Wi, Ci, Co, R, S, stride, pad, &d));
   IEEE_REQUIRE(Co % elem_vec(dtype) == 0, "conv2d_wgrad: Cout must be a multiple of %d", elem_vec(dtype));
-  // the reduction this launch carries as its prologue (wgrad_prologue); kind 0 = none
-  ieee_wgrad_reduce_desc pv;
-  fill_reduce_desc(&pv, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0);
-  if (prev != nullptr && prev->kind != 0) pv = *prev;
   if (const int64_t ssplits = stem_wgrad_splits(dtype, N, Hi, Wi, d.Ho, d.Wo, Ci, Co, R, S, stride, pad)) {
     // the stem: direct form over LDS patches (stem_wgrad_kernel), one slab per STEM_WG_ROWS output rows of an image
     hipStream_t st = (hipStream_t)stream;
-    if (pv.kind != 0) IEEE_TRY(reduce_launch(pv, groups, st));   // (this kernel has no prologue: the pending reduction runs first)
     float* slab = (float*)work;
     const int64_t slab_gs = ssplits * 64 * 256;
     stem_wgrad_kernel<<<dim3((unsigned)ssplits, (unsigned)groups), 256, 12 * 1024 + 16 * 1024, st>>>(
@@ -2571,7 +2356,7 @@ static int wgrad_impl(const void* dy, const void* x, float* dw_oihw, void* work,
   // each weight gradient alone is a little slower (511 vs 515 TFLOP/s serialized), the step is 0.15 ms faster (15.31 -> 15.16,
   // five interleaved rounds): the dgrad / BatchNorm chain finds free slots sooner.  64 KB (2 per CU) loses (15.4).
   static const size_t f_lds = (size_t)(getenv("IEEE_WGRAD_LDS") ? atoi(getenv("IEEE_WGRAD_LDS")) : 48) * 1024;
-  size_t smem = pipe ? (size_t)(pipe == 6 ? 2 : pipe) * 32 * 1024 : (dtype == IEEE_BF16 ? 32 * 1024 : 64 * 1024);
+  size_t smem = pipe ? (size_t)pipe * 32 * 1024 : (dtype == IEEE_BF16 ? 32 * 1024 : 64 * 1024);
   if (smem < f_lds) smem = f_lds;
   static bool attr_done = false;
   if (!attr_done) {
@@ -2630,26 +2415,25 @@ static int wgrad_impl(const void* dy, const void* x, float* dw_oihw, void* work,
     const int wlog = d.Wi == 8 ? 3 : (d.Wi == 16 ? 4 : 5);
     const bool half = d.Co == 64;
 #define IEEE_WP_CASE(W_) \
-    if (half && fold) conv3x3_wgrad_patch_kernel<W_, true, true><<<pgrid, 256, std::max((size_t)(64 * 256 + WPatch<W_>::BYTES), f_lds), st>>>((const bf16*)dy, (const bf16*)x, slab, pa, fa, pv); \
-    else if (fold) conv3x3_wgrad_patch_kernel<W_, false, true><<<pgrid, 256, std::max((size_t)(64 * 256 + WPatch<W_>::BYTES), f_lds), st>>>((const bf16*)dy, (const bf16*)x, slab, pa, fa, pv); \
-    else if (half) conv3x3_wgrad_patch_kernel<W_, true><<<pgrid, 256, std::max((size_t)(64 * 256 + WPatch<W_>::BYTES), f_lds), st>>>((const bf16*)dy, (const bf16*)x, slab, pa, fa, pv); \
-    else conv3x3_wgrad_patch_kernel<W_, false><<<pgrid, 256, std::max((size_t)(64 * 256 + WPatch<W_>::BYTES), f_lds), st>>>((const bf16*)dy, (const bf16*)x, slab, pa, fa, pv)
+    if (half && fold) conv3x3_wgrad_patch_kernel<W_, true, true><<<pgrid, 256, std::max((size_t)(64 * 256 + WPatch<W_>::BYTES), f_lds), st>>>((const bf16*)dy, (const bf16*)x, slab, pa, fa); \
+    else if (fold) conv3x3_wgrad_patch_kernel<W_, false, true><<<pgrid, 256, std::max((size_t)(64 * 256 + WPatch<W_>::BYTES), f_lds), st>>>((const bf16*)dy, (const bf16*)x, slab, pa, fa); \
+    else if (half) conv3x3_wgrad_patch_kernel<W_, true><<<pgrid, 256, std::max((size_t)(64 * 256 + WPatch<W_>::BYTES), f_lds), st>>>((const bf16*)dy, (const bf16*)x, slab, pa, fa); \
+    else conv3x3_wgrad_patch_kernel<W_, false><<<pgrid, 256, std::max((size_t)(64 * 256 + WPatch<W_>::BYTES), f_lds), st>>>((const bf16*)dy, (const bf16*)x, slab, pa, fa)
     if (wlog == 3) { IEEE_WP_CASE(3); } else if (wlog == 4) { IEEE_WP_CASE(4); } else { IEEE_WP_CASE(5); }
 #undef IEEE_WP_CASE
   } else if (dtype == IEEE_F32) {
-    if (slow) conv_wgrad_kernel<float, true><<<grid, 256, smem, st>>>((const float*)dy, (const float*)x, slab, a, pv);
-    else conv_wgrad_kernel<float, false><<<grid, 256, smem, st>>>((const float*)dy, (const float*)x, slab, a, pv);
+    if (slow) conv_wgrad_kernel<float, true><<<grid, 256, smem, st>>>((const float*)dy, (const float*)x, slab, a);
+    else conv_wgrad_kernel<float, false><<<grid, 256, smem, st>>>((const float*)dy, (const float*)x, slab, a);
   } else if (dtype == IEEE_BF16) {
-    if (slow) conv_wgrad_kernel<bf16, true><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, pv);
-    else if (fold && d.Co <= 64) conv_wgrad_fold_kernel<true><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, fa, pv);
-    else if (fold) conv_wgrad_fold_kernel<false><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, fa, pv);
-    else if (pipe == 1 && d.Co <= 64) conv_wgrad_kernel<bf16, false, 1, true><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, pv);
-    else if (pipe == 1) conv_wgrad_kernel<bf16, false, 1><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, pv);
-    else if (pipe == 2) conv_wgrad_kernel<bf16, false, 2><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, pv);
-    else if (pipe == 3) conv_wgrad_kernel<bf16, false, 3><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, pv);
-    else if (pipe == 4) conv_wgrad_kernel<bf16, false, 4><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, pv);
-    else if (pipe == 6) conv_wgrad_kernel<bf16, false, 6><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, pv);
-    else conv_wgrad_kernel<bf16, false><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, pv);
+    if (slow) conv_wgrad_kernel<bf16, true><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a);
+    else if (fold && d.Co <= 64) conv_wgrad_fold_kernel<true><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, fa);
+    else if (fold) conv_wgrad_fold_kernel<false><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, fa);
+    else if (pipe == 1 && d.Co <= 64) conv_wgrad_kernel<bf16, false, 1, true><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a);
+    else if (pipe == 1) conv_wgrad_kernel<bf16, false, 1><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a);
+    else if (pipe == 2) conv_wgrad_kernel<bf16, false, 2><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a);
+    else if (pipe == 3) conv_wgrad_kernel<bf16, false, 3><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a);
+    else if (pipe == 4) conv_wgrad_kernel<bf16, false, 4><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a);
+    else conv_wgrad_kernel<bf16, false><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a);
   } else {
     IEEE_REQUIRE(false, "conv2d_wgrad: bad dtype %d", dtype);
   }
@@ -2713,23 +2497,6 @@ extern "C" int ieee_conv2d_wgrad_deferred(const void* dy, const void* x, float* 
   IEEE_REQUIRE(reduce, "conv2d_wgrad_deferred: null descriptor");
   return wgrad_impl(dy, x, dw_oihw, work, dtype, groups, N, Hi, Wi, Ci, Co, R, S, stride, pad, dy_gs, x_gs, dw_gs, accumulate,
                     stream, reduce);
-}
-
-extern "C" int ieee_conv2d_wgrad_chained(const void* dy, const void* x, float* dw_oihw, void* work, int dtype, int64_t groups,
-                                         int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co, int64_t R, int64_t S,
-                                         int64_t stride, int64_t pad, int64_t dy_gs, int64_t x_gs, int64_t dw_gs,
-                                         int accumulate, const ieee_wgrad_reduce_desc* prev, ieee_wgrad_reduce_desc* reduce,
-                                         void* stream) {
-  IEEE_REQUIRE(reduce, "conv2d_wgrad_chained: null descriptor");
-  IEEE_REQUIRE(prev == nullptr || prev->kind == 0 || (const void*)prev->slab != (const void*)work,
-               "conv2d_wgrad_chained: the pending reduction still reads `work` -- alternate between two slab regions");
-  return wgrad_impl(dy, x, dw_oihw, work, dtype, groups, N, Hi, Wi, Ci, Co, R, S, stride, pad, dy_gs, x_gs, dw_gs, accumulate,
-                    stream, reduce, nullptr, prev);
-}
-
-extern "C" int ieee_wgrad_reduce_pending(const ieee_wgrad_reduce_desc* pending, int64_t groups, void* stream) {
-  IEEE_REQUIRE(pending && groups > 0, "wgrad_reduce_pending: bad arguments");
-  return reduce_launch(*pending, groups, (hipStream_t)stream);
 }
 
 extern "C" int ieee_wgrad_reduce_batch(const ieee_wgrad_reduce_desc* device_descs, int64_t n, int64_t total_blocks, int64_t groups,

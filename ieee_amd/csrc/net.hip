@@ -71,10 +71,6 @@ struct PackDescHost {
 extern "C" int ieee_pack_all_weights(const float* params, void* ws_base, const void* descs, int64_t ndesc,
                                      int64_t total_blocks, int dtype, void* stream);
 
-// IEEE_WGRAD_BATCH: 0 (default) every weight gradient reduces its split-K slabs at once; 1 one batched reduction per
-// backward part (own slab region per unit, +1.7 GB); 2 one per bottleneck block.  Measured: 1 and 2 are 0.1 ms per step
-// SLOWER than 0 (the serialized weight-gradient time improves 1 %, but the large reductions take HBM bandwidth from the
-// dependent chain at once instead of in slices) -- kept as an option of the C ABI, not the default.
 static int gbuf_sets() {
   static const int n = getenv("IEEE_GBUF_SETS") ? atoi(getenv("IEEE_GBUF_SETS")) : 3;
   return n == 2 ? 2 : 3;
@@ -82,21 +78,16 @@ static int gbuf_sets() {
 
 // IEEE_WGRAD_FOLD=1 (default 0): the weight gradients fold their split-K slabs inside their OWN GEMM launch
 // (ieee_conv2d_wgrad_fold: last arriver per output tile).  Parity-green, bit-reproducible, and +0.68 ms per step (LABNOTES R6.1):
-// one reducer per tile is latency-bound.  The default is the chained form below.
+// one reducer per tile is latency-bound.  The default is one reduction launch behind every GEMM.
 static bool wgrad_fold() {
   static const bool on = getenv("IEEE_WGRAD_FOLD") && atoi(getenv("IEEE_WGRAD_FOLD")) != 0;
   return on;
 }
-// IEEE_WGRAD_CHAIN=1 (default 0): every weight-gradient GEMM runs the slab reduction of the PREVIOUS one as its prologue
-// (ieee_conv2d_wgrad_chained; two alternating slab regions); the last reduction of a backward part is flushed as a launch of
-// its own (wgrad_flush).  Same arithmetic as the reduction launches (bit-identical gradients), 46 launches fewer per step --
-// and +0.18 ms per step (14.24 -> 14.42, 4 interleaved rounds, LABNOTES R6.1): a GEMM workgroup that first walks its share of
-// the reduction (a chain of dependent round trips on ~450 workgroups instead of ~2 000 short-lived ones) holds its LDS and
-// registers that much longer.  The reduction launches stay the default.
-static bool wgrad_chain() {
-  static const bool on = getenv("IEEE_WGRAD_CHAIN") && atoi(getenv("IEEE_WGRAD_CHAIN")) != 0;
-  return on;
-}
+
+// IEEE_WGRAD_BATCH: 0 (default) every weight gradient reduces its split-K slabs at once; 1 one batched reduction per
+// backward part (own slab region per unit, +1.7 GB); 2 one per bottleneck block.  Measured: 1 and 2 are 0.1 ms per step
+// SLOWER than 0 (the serialized weight-gradient time improves 1 %, but the large reductions take HBM bandwidth from the
+// dependent chain at once instead of in slices) -- kept as an option of the C ABI, not the default.
 static int wgrad_batch_mode() {
   static const int m = getenv("IEEE_WGRAD_BATCH") ? atoi(getenv("IEEE_WGRAD_BATCH")) : 0;
   return m;
@@ -139,11 +130,7 @@ struct Net {
   const void* rtab_ws[RT_SLOTS] = {};
   ConvUnit reduce_unit;   // profiling label of the batched reductions
   size_t tot_begin = 0, tot_end = 0;   // the units' totals are one contiguous region: ONE memset per training forward
-  Tensor slab2;     // second slab region of the chained weight gradients (wgrad_chain): consecutive launches alternate
-  ieee_wgrad_reduce_desc wpend = {};   // the chained reduction that the next weight-gradient launch (or wgrad_flush) still owes
-  int wflip = 0;
   Tensor wtickets;  // arrival tickets of the weight gradients that fold their split-K slabs themselves (ieee_conv2d_wgrad_fold)
-  Tensor tickets;   // 2 x 256 int32: arrival tickets of the convs that finalize their BatchNorm themselves (launch / branch stream)
   std::vector<PackDescHost> pack_train, pack_eval;   // all units (train: + dgrad operands)
   int pack_blocks_train = 0, pack_blocks_eval = 0;
   // training: the layer3 / layer4 / CIM operands (90 % of the bytes) are packed on the side stream while the
@@ -350,7 +337,6 @@ extern "C" int64_t ieee_conv2d_wgrad_workspace_bytes(int dtype, int64_t groups, 
                                                      int64_t Ci, int64_t Co, int64_t R, int64_t S);
 extern "C" int64_t ieee_bn_partial_floats(int dtype, int64_t M, int64_t C);
 extern "C" int64_t ieee_conv2d_fwd_stats_rblocks(int64_t N, int64_t Ho, int64_t Wo);
-extern "C" int64_t ieee_conv2d_fwd_bn_train_max_rows(void);
 
 void Net::plan() {
   ws_bytes = 0;
@@ -400,7 +386,6 @@ void Net::plan() {
   // buffer is rewritten two blocks after the side-stream wgrad that reads it was issued (one set stalled the chain)
   for (int i = 0; i < NGBUF; ++i) gbuf[i] = alloc("g" + std::to_string(i), max_act, dt);
   slab = alloc("", max_slab / 4 + 64, IEEE_F32);
-  if (wgrad_chain()) slab2 = alloc("", max_slab / 4 + 64, IEEE_F32);
   max_part = std::max(max_part, (int64_t)12 * B * fdim);   // two [3][2][C][B] sets from ieee_cim_tail_bwd_g
   bnpart = alloc("", max_part + 64, IEEE_F32);
   bncoef = alloc("", 3 * 3 * max_c, IEEE_F32);
@@ -444,7 +429,6 @@ void Net::plan() {
   davgmax = alloc("davgmax", 3 * 2 * Bq * fdim, IEEE_F32);
   remwork = alloc("", 3 * Bq + 64, IEEE_F32);
   gemm_work = alloc("", (int64_t)16 << 20, IEEE_F32);  // split-K slabs of the head GEMMs: 2 x 32 MiB (one half per set of a pair)
-  tickets = alloc("", 512, IEEE_F32);
   rtab = alloc("", (int64_t)RT_SLOTS * RT_MAX * sizeof(ieee_wgrad_reduce_desc) / 4, IEEE_F32);
   reduce_unit = ConvUnit();
   reduce_unit.name = "wgrad_reduce_batch";
@@ -460,11 +444,9 @@ struct Run {
   void* st;
   int B;
   float *bnpart_cur, *bncoef_cur;      // BN scratch of the stream `st` currently denotes (see BranchScope)
-  int32_t* tickets_cur;
   Run(Net& net, void* workspace, void* stream) : n(net), ws((char*)workspace), st(stream), B(net.B) {
     bnpart_cur = (float*)(ws + net.bnpart.off);
     bncoef_cur = (float*)(ws + net.bncoef.off);
-    tickets_cur = (int32_t*)(ws + net.tickets.off);
   }
   void* P(const Tensor& t) const { return ws + t.off; }
   float* F(const Tensor& t) const { return (float*)(ws + t.off); }
@@ -540,7 +522,6 @@ struct Run {
   int64_t out_numel(const ConvUnit& u) const { return (int64_t)3 * u.M(B) * u.Co; }
   // fused_stats: the conv epilogue emits the BN partial sums (bf16 training path) -> bn() skips its stats pass
   bool fused_stats = false;
-  bool fused_fin = false;    // ... and finalized them too (ieee_conv2d_fwd_bn_train): bn() only applies
   bool frz(const ConvUnit& u) const { return (n.frozen & u.child) != 0; }
   int totals_rep(const ConvUnit& u) const { return n.totals_off ? 0 : totals_rep_for((u.M(B) + 127) / 128); }
   bool use_totals(const ConvUnit& u) const {
@@ -553,16 +534,8 @@ struct Run {
     const int64_t ldf = ieee_conv_packed_ld(n.dtype, u.Ci, u.R, u.S);
     fused_stats = want_stats && n.dtype == IEEE_BF16 && !frz(u);
     fwd_totals = fused_stats && use_totals(u);
-    // (off by default: correct and bit-reproducible, but measured SLOWER -- 15.40 -> 15.91 ms per step: every workgroup of the
-    // conv has to drain its output stores before it may take its ticket, which costs the conv more than the launch saves)
-    static const bool f_fin = getenv("IEEE_BN_FIN_FUSE") && atoi(getenv("IEEE_BN_FIN_FUSE")) != 0;
-    fused_fin = f_fin && fused_stats && !fwd_totals && u.M(B) <= ieee_conv2d_fwd_bn_train_max_rows() && u.Ci % 64 == 0 && u.Co % 8 == 0;
-    prof_begin(0, u, nullptr, !fused_fin);
+    prof_begin(0, u, nullptr, true);
     struct G { Run* r; ~G() { r->prof_end(); } } guard{this};
-    if (fused_fin)
-      return ieee_conv2d_fwd_bn_train(in, P(u.wf), P(u.y), n.dtype, 3, B, u.Hi, u.Wi, u.Ci, u.Co, u.R, u.S, u.stride, u.pad,
-                                      (int64_t)B * u.Hi * u.Wi * u.Ci, u.Co * ldf, u.M(B) * u.Co, bnpart_cur, par(u.s_g), par(u.s_b),
-                                      gs(u.s_g), buf(u.s_rm), buf(u.s_rv), gs(u.s_rm), F(u.stats), n.bn_mom, n.bn_eps, tickets_cur, st);
     const bool sh = use_shadow && u.shadow_ok;     // Wf[co][ci] of a 1x1 conv = the bf16 image of its OIHW weight
     const void* wf = sh ? (const void*)((const uint16_t*)n.shadow + n.slot_off[u.s_w]) : P(u.wf);
     return ieee_conv2d_fwd_ex(in, wf, P(u.y), n.dtype, 3, B, u.Hi, u.Wi, u.Ci, u.Co, u.R, u.S, u.stride, u.pad,
@@ -572,16 +545,14 @@ struct Run {
   int bn(const ConvUnit& u, const void* residual, void* out, int relu, int training, void* relu_bits = nullptr) {
     if (frz(u)) training = 0;      // frozen child: running statistics, no update (module.eval() in the reference)
     if (training && fwd_totals) {  // statistics in u.tot_f: finalize + apply in one launch
-      fwd_totals = fused_stats = fused_fin = false;
+      fwd_totals = fused_stats = false;
       return ieee_bn2d_fwd_totals(P(u.y), residual, out, n.dtype, 3, u.M(B), u.Co, u.M(B) * u.Co, par(u.s_g), par(u.s_b), gs(u.s_g),
                                   buf(u.s_rm), buf(u.s_rv), gs(u.s_rm), F(u.stats), P(u.tot_f), totals_rep(u), n.bn_mom, n.bn_eps, relu, relu_bits,
                                   oflags_ptr(), st);
     }
     fwd_totals = false;
-    const int64_t rb = (training && fused_fin) ? -1 : ((training && fused_stats) ? ieee_conv2d_fwd_stats_rblocks(B, u.Ho, u.Wo) : 0);
+    const int64_t rb = (training && fused_stats) ? ieee_conv2d_fwd_stats_rblocks(B, u.Ho, u.Wo) : 0;
     fused_stats = false;
-    fused_fin = false;
-    if (rb < 0 && out == nullptr) return IEEE_OK;   // statistics only, and the conv has already finalized them: nothing to launch
     return ieee_bn2d_fwd(P(u.y), residual, out, n.dtype, 3, u.M(B), u.Co, u.M(B) * u.Co, par(u.s_g), par(u.s_b),
                          gs(u.s_g), buf(u.s_rm), buf(u.s_rv), gs(u.s_rm), F(u.stats), bnpart_cur, n.bn_mom, n.bn_eps,
                          training, relu, rb, relu_bits, st);
@@ -729,7 +700,6 @@ struct Run {
       r.st = (void*)r.n.side2;
       r.bnpart_cur = (float*)(r.ws + r.n.bnpart2.off);
       r.bncoef_cur = (float*)(r.ws + r.n.bncoef2.off);
-      r.tickets_cur = (int32_t*)(r.ws + r.n.tickets.off) + 256;
       r.fused_stats = false;
       r.fused_bwd = false;
       r.fwd_totals = false;
@@ -740,7 +710,6 @@ struct Run {
       r.st = main_st;
       r.bnpart_cur = part0;
       r.bncoef_cur = coef0;
-      r.tickets_cur = (int32_t*)(r.ws + r.n.tickets.off);
       r.fused_stats = fs;
       r.fused_bwd = fb;
       r.fwd_totals = ft;
@@ -779,21 +748,10 @@ struct Run {
     struct G { Run* r; ~G() { r->prof_end(); } } guard{this};
     if (u.Ci != u.Ci_src || u.S != u.S_src || u.R != u.R_src) {   // padded stem: gradient of the padded operand, then drop the padding
       const int64_t npad = (int64_t)u.Co * u.Ci * u.R * u.S;
-      IEEE_TRY(wgrad_pending_now());
       IEEE_TRY(ieee_conv2d_wgrad(dy, x, F(u.dwpad), P(n.slab), n.dtype, 3, B, u.Hi, u.Wi, u.Ci, u.Co, u.R, u.S, u.stride,
                                  u.pad, u.M(B) * u.Co, (int64_t)B * u.Hi * u.Wi * u.Ci, npad, 0, st));
       return ieee_unpad_weight_grad(F(u.dwpad), grd(u.s_w), 3, u.Co, u.Ci, u.R, u.S, u.Ci_src, u.R_src, u.S_src, npad, gs(u.s_w), 0,
                                     st);
-    }
-    if (wgrad_batch_mode() == 0 && wgrad_chain()) {
-      ieee_wgrad_reduce_desc d;
-      const int rc = ieee_conv2d_wgrad_chained(dy, x, grd(u.s_w), P(n.wflip ? n.slab2 : n.slab), n.dtype, 3, B, u.Hi, u.Wi, u.Ci, u.Co,
-                                               u.R, u.S, u.stride, u.pad, u.M(B) * u.Co, (int64_t)B * u.Hi * u.Wi * u.Ci, gs(u.s_w), 0,
-                                               n.wpend.kind != 0 ? &n.wpend : nullptr, &d, st);
-      if (rc != IEEE_OK) return rc;       // (n.wpend stays owed: the backward's error path flushes or drops it)
-      n.wpend = d;
-      if (d.kind != 0) n.wflip ^= 1;
-      return IEEE_OK;
     }
     if (wgrad_batch_mode() == 0 && wgrad_fold() && n.dtype == IEEE_BF16)
       return ieee_conv2d_wgrad_fold(dy, x, grd(u.s_w), P(n.slab), (int32_t*)P(n.wtickets), n.dtype, 3, B, u.Hi, u.Wi, u.Ci, u.Co,
@@ -809,25 +767,7 @@ struct Run {
   }
   // The slab reductions of every weight gradient issued since the last flush, as one launch on the stream the weight
   // gradients run on.  slot: which of the step's flush points this is (its descriptor table is cached on the device).
-  // the chained reduction still owed, as a launch of its own on the CURRENT stream `st`
-  int wgrad_pending_now() {
-    if (n.wpend.kind == 0) return IEEE_OK;
-    const ieee_wgrad_reduce_desc d = n.wpend;
-    n.wpend.kind = 0;
-    return ieee_wgrad_reduce_pending(&d, 3, st);
-  }
   int wgrad_flush(int slot) {
-    if (n.wpend.kind != 0) {             // chained form: the last reduction of this group of layers
-      void* main_st = st;
-      const bool on_side = side_enabled();
-      if (on_side) st = (void*)n.side;
-      prof_begin(1, n.reduce_unit, "wgrad_reduce");
-      const int rc = wgrad_pending_now();
-      prof_end();
-      st = main_st;
-      if (on_side) n.side_dirty = true;
-      IEEE_TRY(rc);
-    }
     if (n.rpend.empty()) return IEEE_OK;
     std::vector<ieee_wgrad_reduce_desc> tab;
     tab.swap(n.rpend);
@@ -947,8 +887,6 @@ struct Run {
   bool use_shadow = false;     // this (training) forward reads the 1x1 forward operands from n.shadow
   int forward(const float* xr, const float* xn, const float* xt, int training, float* logits_out, float* feats_out) {
     const int rc = forward_impl(xr, xn, xt, training, logits_out, feats_out);
-    if (rc != IEEE_OK && training)   // an aborted fused-finalize launch may have left arrival tickets behind
-      (void)hipMemsetAsync(P(n.tickets), 0, 512 * 4, (hipStream_t)st);
     if (late_pack_pending) {   // error before layer3: still order the side-stream packing before anything later
       (void)hipStreamWaitEvent((hipStream_t)st, n.pack_ev[1], 0);
       late_pack_pending = false;
@@ -1014,10 +952,6 @@ int Run::forward_impl(const float* xr, const float* xn, const float* xt, int tra
     else if (!(eval_cached = (N.eval_cache_valid && N.eval_cache_ws == (const void*)ws && !N.profiling)))
       IEEE_TRY(ieee_pack_all_weights(N.params, ws, tab_dev, (int64_t)N.pack_eval.size(), N.pack_blocks_eval, dt, st));
     if (training) N.eval_cache_valid = false;     // the step that follows changes parameters and running statistics
-  }
-  {   // arrival tickets of the convs that finalize their BatchNorm themselves: only that (off by default) form reads them
-    static const bool f_fin = getenv("IEEE_BN_FIN_FUSE") && atoi(getenv("IEEE_BN_FIN_FUSE")) != 0;
-    if (training && f_fin) IEEE_HIP(hipMemsetAsync(P(N.tickets), 0, 512 * 4, (hipStream_t)st));
   }
   if (training && dt == IEEE_BF16 && (totals_tiles() > 0 || wgrad_fold())) {   // the units' fixed-point BatchNorm totals (forward AND backward) and the fold tickets start at zero
     IEEE_HIP(hipMemsetAsync(ws + N.tot_begin, 0, N.tot_end - N.tot_begin, (hipStream_t)st));   // (the range-guard flags included)
@@ -1216,7 +1150,6 @@ int Run::backward_impl(const float* dlogits, const float* dfeats, int part) {
                         "its gradients are incomplete -- run the step again");
   }
   if (part <= 0) {
-    N.wpend.kind = 0;   // (a failed backward may have left a chained reduction owed: its gradients are recomputed now)
     // a SECOND backward over the same forward (e.g. two loss terms differentiated one after the other) must not add to
     // the first one's totals: zero them again (the forward's totals were consumed by its BatchNorm passes)
     if (dt == IEEE_BF16 && (totals_tiles() > 0 || wgrad_fold())) {

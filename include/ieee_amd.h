@@ -196,18 +196,6 @@ int ieee_conv2d_fwd(const void* x, const void* w_packed, void* y, int dtype, int
  * sum / sum-of-squares of the stored outputs, rblocks = ieee_conv2d_fwd_stats_rblocks(); hand the same buffer
  * and rblocks to ieee_bn2d_fwd(stats_rblocks) and the separate statistics pass disappears */
 int64_t ieee_conv2d_fwd_stats_rblocks(int64_t N, int64_t Ho, int64_t Wo);
-/* Training forward with the consumer BatchNorm's FINALIZE fused in (bf16, at most ieee_conv2d_fwd_bn_train_max_rows() output
- * pixels per group): besides y and the per-tile partial sums, the launch leaves that BatchNorm's stats [groups][4][Co] (mean,
- * invstd, scale, shift) and updates the running statistics (running_* may be NULL) -- what ieee_bn2d_fwd's finalize step
- * computes (resnet.py:164-184 under nn.BatchNorm2d in train mode); follow with ieee_bn2d_fwd(..., stats_rblocks = -1) for the
- * apply pass only.  `tickets`: groups x ceil(Co / 64) int32, ZERO on entry (the launch leaves them zero again).  The
- * workgroup that arrives last at a column block's ticket reduces that block's partials in tile order (deterministic). */
-int64_t ieee_conv2d_fwd_bn_train_max_rows(void);
-int ieee_conv2d_fwd_bn_train(const void* x, const void* w_packed, void* y, int dtype, int64_t groups, int64_t N, int64_t Hi,
-                             int64_t Wi, int64_t Ci, int64_t Co, int64_t R, int64_t S, int64_t stride, int64_t pad,
-                             int64_t x_gs, int64_t w_gs, int64_t y_gs, float* bn_partial, const float* gamma,
-                             const float* beta, int64_t param_gs, float* running_mean, float* running_var, int64_t buf_gs,
-                             float* stats, float momentum, float eps, int32_t* tickets, void* stream);
 /* inference: conv + eval-mode BatchNorm (+ residual) (+ ReLU) in one launch -- Bottleneck.forward / the stem in eval
  * mode (resnet.py:164-184, 622-626).  bn_stats: that BN's [groups][4][Co] statistics as ieee_bn2d_fwd(training = 0,
  * out = NULL) leaves them (scale at 2*Co, shift at 3*Co); out = [relu](conv(x)*scale + shift [+ residual]). */
@@ -290,20 +278,6 @@ int ieee_conv2d_wgrad_deferred(const void* dy, const void* x, float* dw_oihw, vo
                       ieee_wgrad_reduce_desc* reduce, void* stream);
 int ieee_wgrad_reduce_batch(const ieee_wgrad_reduce_desc* device_descs, int64_t n, int64_t total_blocks, int64_t groups,
                             void* stream);
-/* CHAINED weight gradients (round 6): ieee_conv2d_wgrad_deferred whose launch also runs the reduction `prev` -- the
- * descriptor an EARLIER deferred / chained call on the SAME stream returned; NULL or kind 0: none -- as its PROLOGUE: every
- * workgroup of this GEMM takes a share of that reduction's grid before its own k-loop.  The kernel boundary between the two
- * launches is the only synchronisation (no tickets, no fences), the arithmetic is the reduction launch's (bit-identical
- * gradients), and the ~50 reduction launches of a backward pass disappear from the stream.  Rules: `work` of consecutive
- * chained calls must alternate between two regions (prev's slabs are read while this call's are written; checked); `prev` is
- * always taken care of when the call returns IEEE_OK (a form without a prologue -- the stem -- launches it first); the LAST
- * descriptor of a chain is run by ieee_wgrad_reduce_pending before anything reads that gradient.  Host-side structs, passed
- * by value to the kernels: nothing is uploaded. */
-int ieee_conv2d_wgrad_chained(const void* dy, const void* x, float* dw_oihw, void* work, int dtype, int64_t groups,
-                      int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co, int64_t R, int64_t S,
-                      int64_t stride, int64_t pad, int64_t dy_gs, int64_t x_gs, int64_t dw_gs, int accumulate,
-                      const ieee_wgrad_reduce_desc* prev, ieee_wgrad_reduce_desc* reduce, void* stream);
-int ieee_wgrad_reduce_pending(const ieee_wgrad_reduce_desc* pending, int64_t groups, void* stream);
 
 
 /* ---- BatchNorm2d (+ residual, + ReLU) over NHWC maps [M][C] ------------------ */
@@ -313,7 +287,8 @@ int ieee_wgrad_reduce_pending(const ieee_wgrad_reduce_desc* pending, int64_t gro
  * gamma/beta at param_gs, running stats at buf_gs.
  * stats  : out, groups x [4][C] = mean, invstd, scale, shift (kept for backward)
  * partial: scratch of groups * ieee_bn_partial_floats() floats; with stats_rblocks > 0 it already holds the
- *          [2][C][stats_rblocks] sums emitted by ieee_conv2d_fwd and the statistics kernel is skipped
+ *          [2][C][stats_rblocks] sums emitted by ieee_conv2d_fwd and the statistics kernel is skipped;
+ *          stats_rblocks < 0 (training): `stats` is final as the caller hands it in, the apply pass only
  * out = [relu]( y*scale + shift [+ residual] ); out NULL = statistics only.  training=0 uses running stats. */
 int64_t ieee_bn_partial_floats(int dtype, int64_t M, int64_t C);
 int ieee_bn2d_fwd(const void* y, const void* residual, void* out, int dtype, int64_t groups, int64_t M,

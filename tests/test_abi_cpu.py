@@ -67,7 +67,7 @@ def test_loading_the_library_brings_torch_in_first():
 
 def test_struct_layouts_match_the_header(tmp_path):
     """the ctypes mirrors of the header's structs (ieee_conv_extras of the explicit-argument conv calls, ieee_wgrad_reduce_desc
-    of the deferred / chained weight gradients) against what a C compiler makes of include/ieee_amd.h: size and every offset"""
+    of the deferred weight gradients) against what a C compiler makes of include/ieee_amd.h: size and every offset"""
     import subprocess
     from ieee_amd import _lib
     fields = {"ieee_conv_extras": [f[0] for f in _lib.ConvExtras._fields_],

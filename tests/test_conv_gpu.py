@@ -137,47 +137,6 @@ def test_padded_stem_equals_7x7_conv(dtype, form):
         torch.testing.assert_close(dw[i].cpu(), refs[i][2], **wtol)
 
 
-@pytest.mark.parametrize("N,H", [(2, 32), (3, 16), (3, 24), (1, 4)])
-def test_direct_stem_persistent_over_four_tiles(N, H):
-    """the direct stem kernel at the executor's width (W = 128 -> 64 output columns): bf16, 8x8 / stride 2 over the
-    border-padded 4-channel image, with the fused BatchNorm sums.  H = 32 / 16: the workgroup walks 4 tiles (8 output rows)
-    with the weights in registers and the next patch prefetched; H = 24 / 4 (6 tiles / 1 tile per image: not a multiple of 4): the
-    one-tile-per-workgroup form.  Against torch's fp32 conv on the bf16-rounded operands, and the per-tile sums against
-    the stored output."""
-    from ieee_amd import _lib as L
-    lib = L.require_gpu()
-    g = torch.Generator().manual_seed(17)
-    rt = lambda t: t.to(torch.bfloat16).float()
-    G, W, Co = 3, 128, 64
-    x = rt(torch.randn(G, N, 3, H, W, generator=g))
-    w = rt(torch.randn(G, Co, 3, 7, 7, generator=g) * 0.1)
-    xs = [x[i].contiguous().cuda() for i in range(G)]
-    Hp, Wp = H + 6, W + 6
-    xp = torch.empty((G, N, Hp, Wp, 4), device="cuda", dtype=torch.bfloat16)
-    L.check(lib.ieee_nchw_to_nhwc3(L.ptr(xs[0]), L.ptr(xs[1]), L.ptr(xs[2]), L.ptr(xp), L.IEEE_BF16, N, 3, H, W, 4, 3, L.stream()))
-    ld = lib.ieee_conv_packed_ld(L.IEEE_BF16, 4, 8, 8)
-    wp = torch.empty(G, Co, ld, device="cuda", dtype=torch.bfloat16)
-    wd = w.cuda().contiguous()
-    L.check(lib.ieee_pack_conv_weight_padded(L.ptr(wd), L.ptr(wp), L.IEEE_BF16, 0, G, Co, 3, 7, 7, 4, 8, 8, Co * 3 * 49, Co * ld, L.stream()))
-    Ho, Wo = H // 2, W // 2
-    rb = lib.ieee_conv2d_fwd_stats_rblocks(N, Ho, Wo)
-    for stats in (False, True):
-        y = torch.full((G, N, Ho, Wo, Co), 9.0, device="cuda", dtype=torch.bfloat16)
-        part = torch.zeros(G, 2, Co, rb, device="cuda")
-        L.check(lib.ieee_conv2d_fwd(L.ptr(xp), L.ptr(wp), L.ptr(y), L.IEEE_BF16, G, N, Hp, Wp, 4, Co, 8, 8, 2, 0, xp[0].numel(), Co * ld,
-                                    y[0].numel(), L.ptr(part) if stats else None, L.stream()))
-        for i in range(G):
-            ref = torch.nn.functional.conv2d(x[i], w[i], None, 2, 3).permute(0, 2, 3, 1)
-            torch.testing.assert_close(y[i].float().cpu(), ref, rtol=2e-2, atol=3e-2)
-        if stats:
-            yf = y.float().view(G, -1, Co)
-            torch.testing.assert_close(part[:, 0].sum(-1), yf.sum(1), rtol=1e-4, atol=2e-2)
-            torch.testing.assert_close(part[:, 1].sum(-1), (yf * yf).sum(1), rtol=1e-4, atol=2e-2)
-            # per tile (128 rows = 2 output rows), not only in total: a walking workgroup must file each tile's sums under its own index
-            tiles = yf.view(G, rb, 128, Co)
-            torch.testing.assert_close(part[:, 0].permute(0, 2, 1), tiles.sum(2), rtol=1e-4, atol=2e-2)
-
-
 def test_fused_bn_partials_in_conv_epilogues():
     """bf16: the forward epilogue's per-tile BN sums (sum y, sum y^2) and the dgrad epilogue's BN-backward sums
     (sum g, sum g*y with the three mask sources) against direct sums over the tensors the kernels stored"""
@@ -362,54 +321,6 @@ def test_conv_with_fused_eval_batchnorm(dtype, res, relu):
         torch.testing.assert_close(out[i].float().cpu().permute(0, 3, 1, 2), want[i], **tol)
 
 
-@pytest.mark.parametrize("R,Ci,Co,H,W", [(1, 128, 320, 16, 8), (3, 64, 128, 16, 8), (3, 128, 64, 8, 16)])
-def test_conv_with_fused_train_batchnorm_finalize(R, Ci, Co, H, W):
-    """ieee_conv2d_fwd_bn_train (the BatchNorm finalize done by the last-arriving workgroup of each column block) against
-    the two-launch form -- ieee_conv2d_fwd with partial sums + ieee_bn2d_fwd's finalize: same y bit for bit, the same
-    statistics / scale / shift / running statistics up to the summation order of the per-tile partials (float64 on both
-    sides), tickets left at zero; twice in a row (the second launch reuses the tickets the first one reset)."""
-    from ieee_amd import _lib as L, _ops
-    lib = L.require_gpu()
-    g = torch.Generator().manual_seed(R * 100 + Co)
-    G, N = 3, 20                                        # M = 2560 rows: 20 row tiles
-    dt = torch.bfloat16
-    pad = R // 2
-    x = torch.randn(G, N, H, W, Ci, generator=g).cuda().to(dt)
-    w = (torch.randn(G, Co, Ci, R, R, generator=g) * (2.0 / (Ci * R * R)) ** 0.5).cuda()
-    wp = _ops.pack_conv_weight(w, dt, 0)
-    M = N * H * W
-    assert M <= lib.ieee_conv2d_fwd_bn_train_max_rows()
-    rb = lib.ieee_conv2d_fwd_stats_rblocks(N, H, W)
-    gam, bet = torch.rand(G, Co, generator=g).cuda() + 0.5, torch.randn(G, Co, generator=g).cuda()
-    rm0, rv0 = torch.randn(G, Co, generator=g).cuda(), torch.rand(G, Co, generator=g).cuda() + 0.5
-    # two launches
-    part = torch.zeros(G, 2, Co, rb, device="cuda")
-    y_a = torch.empty(G, N, H, W, Co, device="cuda", dtype=dt)
-    L.check(lib.ieee_conv2d_fwd(L.ptr(x), L.ptr(wp), L.ptr(y_a), L.IEEE_BF16, G, N, H, W, Ci, Co, R, R, 1, pad, x[0].numel(),
-                                wp.stride(0), y_a[0].numel(), L.ptr(part), L.stream()))
-    st_a, rm_a, rv_a = torch.zeros(G, 4, Co, device="cuda"), rm0.clone(), rv0.clone()
-    L.check(lib.ieee_bn2d_fwd(L.ptr(y_a), None, None, L.IEEE_BF16, G, M, Co, M * Co, L.ptr(gam), L.ptr(bet), Co, L.ptr(rm_a),
-                              L.ptr(rv_a), Co, L.ptr(st_a), L.ptr(part), 0.1, 1e-5, 1, 1, rb, None, L.stream()))
-    # one launch, twice
-    tickets = torch.zeros(G * ((Co + 63) // 64), dtype=torch.int32, device="cuda")
-    for rep in range(2):
-        part_b = torch.zeros_like(part)
-        y_b = torch.empty_like(y_a)
-        st_b, rm_b, rv_b = torch.zeros_like(st_a), rm0.clone(), rv0.clone()
-        L.check(lib.ieee_conv2d_fwd_bn_train(L.ptr(x), L.ptr(wp), L.ptr(y_b), L.IEEE_BF16, G, N, H, W, Ci, Co, R, R, 1, pad,
-                                             x[0].numel(), wp.stride(0), y_b[0].numel(), L.ptr(part_b), L.ptr(gam), L.ptr(bet), Co,
-                                             L.ptr(rm_b), L.ptr(rv_b), Co, L.ptr(st_b), 0.1, 1e-5, L.ptr(tickets), L.stream()))
-        torch.cuda.synchronize()
-        assert torch.equal(y_a, y_b) and torch.equal(part, part_b)
-        assert int(tickets.abs().sum()) == 0
-        torch.testing.assert_close(st_b, st_a, rtol=2e-6, atol=1e-6)
-        torch.testing.assert_close(rm_b, rm_a, rtol=2e-6, atol=1e-7)
-        torch.testing.assert_close(rv_b, rv_a, rtol=2e-6, atol=1e-7)
-    # and the statistics are the batch statistics of the stored y
-    yf = y_a.float().view(G, M, Co)
-    torch.testing.assert_close(st_a[:, 0], yf.mean(1), rtol=1e-4, atol=1e-4)
-
-
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_deferred_wgrad_with_one_batched_reduction_is_bit_identical(dtype):
     """ieee_conv2d_wgrad_deferred + ONE ieee_wgrad_reduce_batch over several layers (what the executor does per backward
@@ -457,57 +368,6 @@ def test_deferred_wgrad_with_one_batched_reduction_is_bit_identical(dtype):
     torch.cuda.synchronize()
     for (x, dy, work, out), ref in zip(keep, want):
         assert torch.equal(out, ref)
-
-
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-def test_chained_wgrad_runs_the_previous_reduction_as_its_prologue_bit_identical(dtype):
-    """ieee_conv2d_wgrad_chained: every launch folds the slabs of the PREVIOUS layer before its own GEMM (two alternating slab
-    regions), the last descriptor is flushed by ieee_wgrad_reduce_pending.  Same kernels' arithmetic as the immediate
-    ieee_conv2d_wgrad -> the same bits, for every reduction form, with and without `accumulate`, and a refused call when the
-    pending reduction still reads the region handed in as `work`."""
-    import ctypes
-    from ieee_amd import _lib as L
-    lib = L.require_gpu()
-    g = torch.Generator().manual_seed(12)
-    dt = L.IEEE_BF16 if dtype == torch.bfloat16 else L.IEEE_F32
-    #        N   H   W   Ci   Co   R  stride pad
-    layers = [(8, 16, 8, 256, 64, 1, 1, 0), (8, 16, 8, 64, 64, 3, 1, 1), (8, 16, 8, 512, 512, 3, 1, 1), (16, 8, 8, 1024, 256, 1, 1, 0),
-              (2, 16, 8, 256, 512, 1, 2, 0), (3, 5, 7, 64, 128, 3, 1, 1), (2, 70, 134, 4, 64, 8, 2, 0), (8, 32, 16, 8, 64, 7, 2, 3),
-              (64, 32, 16, 64, 256, 1, 1, 0), (64, 16, 8, 2048, 2048, 1, 1, 0), (64, 16, 8, 256, 256, 3, 1, 1)]
-    G = 3
-    big = max(lib.ieee_conv2d_wgrad_workspace_bytes(dt, G, N, (H + 2 * pad - R) // st + 1, (W + 2 * pad - R) // st + 1, Ci, Co, R, R)
-              for (N, H, W, Ci, Co, R, st, pad) in layers)
-    regions = [torch.empty(big, dtype=torch.uint8, device="cuda") for _ in range(2)]
-    flip, pend, keep, want, kinds = 0, None, [], [], set()
-    for (N, H, W, Ci, Co, R, stride, pad) in layers:
-        Ho, Wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
-        x = torch.randn(G, N, H, W, Ci, generator=g).cuda().to(dtype)
-        dy = torch.randn(G, N, Ho, Wo, Co, generator=g).cuda().to(dtype)
-        args = (dt, G, N, H, W, Ci, Co, R, R, stride, pad, dy[0].numel(), x[0].numel(), Co * Ci * R * R)
-        for acc in (0, 1):
-            base = torch.randn(G, Co, Ci, R, R, generator=g).cuda()
-            ref, out = base.clone(), base.clone()
-            work0 = torch.empty(big, dtype=torch.uint8, device="cuda")
-            L.check(lib.ieee_conv2d_wgrad(L.ptr(dy), L.ptr(x), L.ptr(ref), L.ptr(work0), *args, acc, L.stream()))
-            d = L.WgradReduceDesc()
-            if pend is not None:       # the region the pending reduction reads must not be handed in again
-                rc = lib.ieee_conv2d_wgrad_chained(L.ptr(dy), L.ptr(x), L.ptr(out), L.ptr(regions[flip ^ 1]), *args, acc,
-                                                   ctypes.addressof(pend), ctypes.addressof(d), L.stream())
-                assert rc != 0 and b"alternate" in lib.ieee_last_error()
-            L.check(lib.ieee_conv2d_wgrad_chained(L.ptr(dy), L.ptr(x), L.ptr(out), L.ptr(regions[flip]), *args, acc,
-                                                  ctypes.addressof(pend) if pend is not None else None, ctypes.addressof(d),
-                                                  L.stream()))
-            kinds.add(d.kind)
-            pend = d if d.kind != 0 else None
-            if d.kind != 0:
-                flip ^= 1
-            keep.append((x, dy, out)); want.append(ref)
-    if pend is not None:
-        L.check(lib.ieee_wgrad_reduce_pending(ctypes.addressof(pend), G, L.stream()))
-    torch.cuda.synchronize()
-    assert ({0, 1, 2, 3} if dtype == torch.bfloat16 else {1, 2}) <= kinds, kinds
-    for i, ((x, dy, out), ref) in enumerate(zip(keep, want)):
-        assert torch.equal(out, ref), "layer %d" % (i // 2)
 
 
 @pytest.mark.parametrize("Ci,Co,R,H,W,REP", [(64, 256, 1, 16, 8, 1), (128, 128, 3, 16, 8, 1), (256, 64, 1, 12, 10, 1), (64, 256, 1, 16, 8, 8),
