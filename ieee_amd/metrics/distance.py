@@ -24,37 +24,55 @@ PRECISIONS = ("fp32", "bf16x3", "f16x2", "bf16x2", "bf16")
 _SPLIT_SCHEME = {"bf16x3": 6, "bf16x2": 3, "f16x2": 2}     # IEEE_SPLIT_* in include/ieee_amd.h
 
 
-def _distmat(input1, input2, metric_id, compute_dtype=None, precision=None):
-    lib = _lib.require_gpu()
+def _resolve(precision, input_dtype, compute_dtype=None):
+    """-> (precision, compute_dtype): the environment's default, the known values, bf16 for bf16 inputs"""
     if precision is None:
         precision = os.environ.get("IEEE_DISTMAT_PRECISION", "fp32")
     if precision not in PRECISIONS:
         raise ValueError("Unknown distmat precision: {}. Choose one of {}".format(precision, PRECISIONS))
     if compute_dtype is None:
-        compute_dtype = torch.bfloat16 if (input1.dtype == torch.bfloat16 or precision == "bf16") else torch.float32
+        compute_dtype = torch.bfloat16 if (input_dtype == torch.bfloat16 or precision == "bf16") else torch.float32
+    return precision, compute_dtype
+
+
+def _pad8(x):
+    """kernels move 16-byte chunks: pad the feature axis with zeros (changes nothing)"""
+    d = x.shape[1]
+    return x if d % 8 == 0 else torch.nn.functional.pad(x, (0, 8 - d % 8))
+
+
+def _workspace_bytes(lib, m, n, d, compute_dtype, precision):
+    if compute_dtype == torch.float32 and precision in _SPLIT_SCHEME:
+        return lib.ieee_sqeuclid_distmat_split_workspace_bytes(m, n, d, _SPLIT_SCHEME[precision])
+    return (m + n) * 4
+
+
+def _launch(lib, a, b, metric_id, compute_dtype, precision, out, ldo, work):
+    """a [m, d], b [n, d]: contiguous device rows of compute_dtype, d % 8 == 0; out: fp32, row stride ldo >= n;
+    work: a device buffer of at least _workspace_bytes(...) bytes"""
+    (m, d), n = a.shape, b.shape[0]
+    if compute_dtype == torch.float32 and precision in _SPLIT_SCHEME:
+        _lib.check(lib.ieee_sqeuclid_distmat_split(_lib.ptr(a), _lib.ptr(b), m, n, d, _SPLIT_SCHEME[precision], metric_id,
+                                                   _lib.ptr(out), ldo, _lib.ptr(work), work.numel() * work.element_size(),
+                                                   _lib.stream()))
+        return
+    dt = _lib.IEEE_BF16 if compute_dtype == torch.bfloat16 else _lib.IEEE_F32
+    _lib.check(lib.ieee_sqeuclid_distmat(_lib.ptr(a), _lib.ptr(b), m, n, d, dt, metric_id, _lib.ptr(out), ldo,
+                                         _lib.ptr(work), _lib.stream()))
+
+
+def _distmat(input1, input2, metric_id, compute_dtype=None, precision=None):
+    lib = _lib.require_gpu()
+    precision, compute_dtype = _resolve(precision, input1.dtype, compute_dtype)
     a, dev = _as_device(input1, compute_dtype)
     b, _ = _as_device(input2, compute_dtype)
-    m, d = a.shape
-    n = b.shape[0]
+    m, n = a.shape[0], b.shape[0]
     out = torch.empty((m, n), dtype=torch.float32, device=a.device)
     if m == 0 or n == 0:
         return out.to(dev)
-    if d % 8 != 0:   # kernels move 16-byte chunks: pad the feature axis with zeros (changes nothing)
-        pad = 8 - d % 8
-        a = torch.nn.functional.pad(a, (0, pad))
-        b = torch.nn.functional.pad(b, (0, pad))
-        d += pad
-    if compute_dtype == torch.float32 and precision in _SPLIT_SCHEME:
-        terms = _SPLIT_SCHEME[precision]
-        nbytes = lib.ieee_sqeuclid_distmat_split_workspace_bytes(m, n, d, terms)
-        work = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
-        _lib.check(lib.ieee_sqeuclid_distmat_split(_lib.ptr(a), _lib.ptr(b), m, n, d, terms, metric_id, _lib.ptr(out), n,
-                                                   _lib.ptr(work), nbytes, _lib.stream()))
-        return out if dev.type == "cuda" else out.to(dev)
-    work = torch.empty(m + n, dtype=torch.float32, device=a.device)
-    dt = _lib.IEEE_BF16 if compute_dtype == torch.bfloat16 else _lib.IEEE_F32
-    _lib.check(lib.ieee_sqeuclid_distmat(_lib.ptr(a), _lib.ptr(b), m, n, d, dt, metric_id, _lib.ptr(out), n,
-                                         _lib.ptr(work), _lib.stream()))
+    a, b = _pad8(a), _pad8(b)
+    work = torch.empty(_workspace_bytes(lib, m, n, a.shape[1], compute_dtype, precision), dtype=torch.uint8, device=a.device)
+    _launch(lib, a, b, metric_id, compute_dtype, precision, out, n, work)
     return out if dev.type == "cuda" else out.to(dev)
 
 

@@ -41,17 +41,34 @@ def _tile(path, width, height, color):
     return np.asarray(img.resize((width, height), Image.BILINEAR))
 
 
-def visualize_ranked_results(distmat, dataset, data_type='image', width=128, height=256, save_dir='', topk=10):
+def visualize_ranked_results(distmat, dataset, data_type='image', width=128, height=256, save_dir='', topk=10,
+                             indices=None):
     """Draws, for every query, its image and its top-k kept gallery images in one row (green border: same identity,
     red: another identity) into <save_dir>/<basename of the query's first image>.jpg.
 
     distmat: [num_query, num_gallery] distances, a CUDA tensor or a numpy array.  dataset: (query, gallery), each a
-    list of (img_paths, pid, camid, ...) records.  Returns the ranked gallery indices drawn for every query."""
+    list of (img_paths, pid, camid, ...) records.  Returns the ranked gallery indices drawn for every query.
+
+    indices (not in the reference): with distmat=None, a ranking that exists already, [num_query, topk] gallery indices
+    with -1 for no entry -- what ieee_amd.metrics.search_topk returns without ever forming the matrix.  It is drawn as
+    it is (the first topk columns): nothing is ranked or filtered here.  Give exactly one of distmat and indices."""
     from PIL import Image
-    from .metrics.topk import rank_topk
     if data_type != 'image':
         raise NotImplementedError("visualize_ranked_results: data_type=%r; only image re-id is supported" % (data_type,))
-    num_q, num_g = distmat.shape
+    if (distmat is None) == (indices is None):
+        raise ValueError("visualize_ranked_results: give either distmat or indices, not %s" %
+                         ("both" if distmat is not None else "neither"))
+    if indices is not None:
+        indices = np.asarray(indices.detach().cpu().numpy() if hasattr(indices, 'detach') else indices)
+        if indices.ndim != 2 or indices.shape[0] != len(dataset[0]) or indices.dtype.kind not in 'iu':
+            raise ValueError("visualize_ranked_results: indices must be integers [%d, topk], got %s %s"
+                             % (len(dataset[0]), indices.dtype, indices.shape))
+        if indices.size and (indices.max() >= len(dataset[1]) or indices.min() < -1):
+            raise ValueError("visualize_ranked_results: indices must lie in [-1, %d)" % len(dataset[1]))
+        indices = indices[:, :topk]
+        num_q, num_g = indices.shape[0], len(dataset[1])
+    else:
+        num_q, num_g = distmat.shape
     os.makedirs(save_dir or '.', exist_ok=True)
 
     print('# query: {}\n# gallery {}'.format(num_q, num_g))
@@ -65,8 +82,10 @@ def visualize_ranked_results(distmat, dataset, data_type='image', width=128, hei
     q_camids = np.asarray([r[2] for r in query], dtype=np.int64)
     g_pids = np.asarray([r[1] for r in gallery], dtype=np.int64)
     g_camids = np.asarray([r[2] for r in gallery], dtype=np.int64)
-    indices, _ = rank_topk(distmat, topk, q_pids, g_pids, q_camids, g_camids)
-    indices = indices.cpu().numpy()
+    if indices is None:
+        from .metrics.topk import rank_topk
+        indices, _ = rank_topk(distmat, topk, q_pids, g_pids, q_camids, g_camids)
+        indices = indices.cpu().numpy()
 
     ranked = []
     for q_idx in range(num_q):

@@ -105,6 +105,21 @@ int ieee_rank_topk(const float* distmat, int64_t ldd, int64_t num_q, int64_t num
                    const int32_t* q_pids, const int32_t* g_pids, const int32_t* q_camids,
                    const int32_t* g_camids, int exclude_same_cam, int64_t k, int32_t* out_idx,
                    float* out_dist, void* stream);
+/* ieee_rank_topk continued from a previous result: gallery search without the whole [num_q][num_g] matrix.
+ * slab [num_q][slab_g] fp32 (row stride ldd >= slab_g) holds the distances to gallery entries g_base ... g_base +
+ * slab_g - 1; slab_g_pids / slab_g_camids are the labels of those entries only (indexed by the slab's column).
+ * state_idx int32 / state_dist fp32, [num_q][k] row-major, hold the list so far and are updated in place: each row
+ * ascending in (distance, GLOBAL gallery index), unused places idx -1 / dist +inf at the end.  A search starts from a
+ * state filled with -1 / +inf.  Precondition (not checked): every index in the state is < g_base.  After the slabs of
+ * any partition of a matrix's columns have been merged in ascending g_base order the state equals ieee_rank_topk's
+ * result for the whole matrix bit for bit: ties go to the smaller global index, and a distance that entered the list
+ * slabs ago comes back with its own bits (-0.0, NaN payloads).  1 <= k <= 1024, g_base >= 0 and
+ * g_base + slab_g < 2^31 - 6144, else IEEE_ERR_BAD_ARG before any launch; num_q == 0 or slab_g == 0 is a no-op.
+ * No workspace, no host sync, no atomics on global memory: the same bits on every call. */
+int ieee_rank_topk_merge(const float* slab, int64_t ldd, int64_t num_q, int64_t slab_g, int64_t g_base,
+                         const int32_t* q_pids, const int32_t* slab_g_pids, const int32_t* q_camids,
+                         const int32_t* slab_g_camids, int exclude_same_cam, int64_t k, int32_t* state_idx,
+                         float* state_dist, void* stream);
 /* CUHK03 single-gallery-shot protocol, torchreid/metrics/rank.py:24-100 (eval_cuhk03 with the time-id filter): the
  * EXPECTED curve of the protocol's random draw (one gallery image per identity, uniformly), not a 10-sample estimate
  * of it.  distmat [num_q][num_g] fp32 (row stride ldd >= num_g); q_pids / g_pids int32; q_keys / g_keys int32, one
