@@ -236,73 +236,8 @@ __global__ __launch_bounds__(256) void split_rows_f16_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------- CMC / mAP
-constexpr int RANK_CAP = 1024;    // match keys sorted per batch (LDS)
-constexpr int RANK_CELLS = 512;   // distance cells over the batch's match range
-constexpr int RANK_UNR = 8;       // 16-byte loads per thread in flight in rank_query_fast_kernel's stream
-
-// the Market protocol orders on the raw IEEE total order (rank_common.h says why)
-__device__ __forceinline__ uint64_t make_key(float d, uint32_t idx) { return order_key(order_word_raw(d), idx); }
-
-// Cell of a distance on the uniform grid laid over [dmin, dmax] of a batch's sorted match keys.  Every step
-// (subtract a constant, multiply by a non-negative constant, min, truncate) is monotone under rounding, so
-// a < b implies cell(a) <= cell(b): keys in lower cells are smaller, keys in higher cells are larger, and only
-// the keys sharing the element's cell have to be compared.
-__device__ __forceinline__ uint32_t rank_cell(float d, float dmin, float scale) {
-  return (uint32_t)(int)fminf((d - dmin) * scale, (float)(RANK_CELLS - 1));   // NaN -> last cell
-}
-
-// ---- the batch core of the two query kernels: what they do with a batch of nb <= RANK_CAP match keys is the same;
-// how the keys are collected, what an element adds to hist and how the removed entries leave it is theirs.
-struct RankGrid {
-  uint64_t kmin, kmax;       // the batch's smallest and largest match key
-  float dmin, dmax, scale;   // their distances, and cells per unit of distance
-  uint32_t hlen;             // words of hist in use: slots 0 .. RANK_CELLS + nb + 1
-};
-
-// keys[0, nb) are the batch's match keys in any order, written by the caller and not yet synchronised (the first
-// barrier is lds_bitonic_sort's; it also covers what the caller cleared just before the call).  On return the keys are
-// sorted, hist is zero up to its scan slack, cellinfo[c] = first key index of cell c | keys in the cell << 16, and all
-// of it is visible to the block.
-__device__ __forceinline__ RankGrid rank_prepare_batch(uint64_t* keys, uint32_t nb, uint32_t* hist, uint32_t* cellinfo,
-                                                       uint32_t* wsum) {
-  const uint32_t t = threadIdx.x;
-  RankGrid g;
-  g.hlen = RANK_CELLS + nb + 2;
-  for (uint32_t i = t; i < g.hlen + 512; i += 256) hist[i] = 0;
-  for (uint32_t i = t; i < RANK_CELLS; i += 256) cellinfo[i] = 0;
-  lds_bitonic_sort<256>(keys, nb);
-  g.kmin = keys[0];
-  g.kmax = keys[nb - 1];
-  g.dmin = key_dist(g.kmin);
-  g.dmax = key_dist(g.kmax);
-  g.scale = (float)RANK_CELLS / (g.dmax - g.dmin);
-  if (!(g.scale < 1e30f)) g.scale = 0.f;         // one distinct distance (or inf/NaN): a single cell
-  // count the keys of every cell, then an exclusive scan gives the first key of each
-  for (uint32_t i = t; i < nb; i += 256) atomicAdd(&cellinfo[rank_cell(key_dist(keys[i]), g.dmin, g.scale)], 1u);
-  __syncthreads();
-  constexpr int PER = RANK_CELLS / 256;
-  uint32_t c[PER], sum = 0;
-#pragma unroll
-  for (int e = 0; e < PER; ++e) { c[e] = cellinfo[t * PER + e]; sum += c[e]; }
-  uint32_t tot;
-  uint32_t run = block_scan_excl(sum, wsum, &tot);
-#pragma unroll
-  for (int e = 0; e < PER; ++e) { cellinfo[t * PER + e] = run | (c[e] << 16); run += c[e]; }
-  __syncthreads();
-  return g;
-}
-
-// inclusive prefix sums over hist[0, hlen) in place: a contiguous odd-length span per thread (conflict-free; the spans
-// reach into hist's 512 words of slack, which are zero)
-__device__ __forceinline__ void rank_scan_hist(uint32_t* hist, uint32_t hlen, uint32_t* wsum) {
-  const uint32_t t = threadIdx.x, per = ((hlen + 255) / 256) | 1u;
-  uint32_t sum = 0;
-  for (uint32_t e = 0; e < per; ++e) sum += hist[t * per + e];
-  uint32_t tot;
-  uint32_t run = block_scan_excl(sum, wsum, &tot);
-  for (uint32_t e = 0; e < per; ++e) { run += hist[t * per + e]; hist[t * per + e] = run; }
-  __syncthreads();
-}
+// (the batch core -- RANK_CAP, RANK_CELLS, make_key, rank_cell, RankGrid, rank_prepare_batch, rank_scan_hist -- is in
+// rank_common.h: rank_stream.hip runs it on gallery slabs)
 
 // ---- identity buckets: gallery indices grouped by a hash of their identity (counting sort, order inside a bucket
 // arbitrary -- the consumers sort what they collect).  work: start[RANK_BUCKETS + 1], cursor[RANK_BUCKETS], idx[num_g].
@@ -657,6 +592,13 @@ __global__ __launch_bounds__(256) void rank_finalize_kernel(const double* ap, co
     summary[max_rank] = (int64_t)nsum[0];
     summary[max_rank + 1] = __double_as_longlong(dsum[0]);
   }
+}
+
+// the same kernel for rank_stream.hip (declared in rank_common.h), so that both evaluations sum in one association
+int rank_finalize_launch(const double* ap, const int32_t* first, int64_t num_q, int64_t max_rank, int64_t* summary,
+                         hipStream_t stream) {
+  rank_finalize_kernel<<<1, 256, 0, stream>>>(ap, first, (int)num_q, (int)max_rank, summary);
+  return launch_status("rank_finalize");
 }
 
 }  // namespace ieee

@@ -30,7 +30,7 @@ from .losses import (CrossEntropyLoss, DeepSupervision, TripletLoss, chunks_shor
                      multiModalMarginLossNew, single_identity, single_identity_error, target_out_of_range,
                      triplet_work_floats)
 from .meters import AverageMeter, DeferredSummary, MetricMeter
-from .metrics import accuracy, compute_distance_matrix, evaluate_rank
+from .metrics import accuracy, compute_distance_matrix, evaluate_rank, evaluate_rank_streamed
 from .optim import FUSED_OPTIMIZERS, FusedSGD
 
 _Entry = namedtuple("_Entry", "model optim sched")
@@ -46,6 +46,21 @@ def _check_rerank(rerank):
     """rerank is False / True (k-reciprocal) or the string 'gnn'; values that are not strings keep their truthiness"""
     if isinstance(rerank, str) and rerank != 'gnn':
         raise ValueError("rerank must be False, True (k-reciprocal re-ranking) or 'gnn', got {!r}".format(rerank))
+
+
+def _check_stream_eval(stream_eval, rerank, use_metric_cuhk03):
+    """stream_eval is the Market1501 protocol on one rank, on plain distances"""
+    if not stream_eval:
+        return
+    if rerank:
+        raise ValueError('stream_eval=True cannot be combined with rerank: re-ranking needs the whole distance matrix, '
+                         'which a streamed evaluation never forms')
+    if use_metric_cuhk03:
+        raise ValueError('stream_eval=True evaluates the Market1501 protocol only: use_metric_cuhk03=True needs '
+                         'stream_eval=False')
+    if ddp.world_size() > 1:
+        raise ValueError('stream_eval=True runs on one rank; over {} ranks the query-sharded evaluation already divides '
+                         'the distance matrix by the world size'.format(ddp.world_size()))
 
 
 class Engine(object):
@@ -125,18 +140,19 @@ class Engine(object):
     def run(self, save_dir='log', max_epoch=0, start_epoch=0, print_freq=10, fixbase_epoch=0, open_layers=None,
             start_eval=0, eval_freq=-1, test_only=False, dist_metric='euclidean', normalize_feature=False,
             visrank=False, visrank_topk=10, use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False,
-            rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None):
+            rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None, stream_eval=False):
         """engine.py:126-232.  As in the reference there is NO evaluation or checkpoint after the last epoch (the
         `(epoch + 1) != max_epoch` guard, :216), and re-ranking applies to test_only runs (its docstring, :171-172;
         the in-loop test call does not pass it on, :217-225).  rerank: False, True (k-reciprocal) or 'gnn' (see test;
-        rerank_k1 / rerank_k2 belong to 'gnn' alone).  vistsne / vistsne_labels: see test."""
+        rerank_k1 / rerank_k2 belong to 'gnn' alone).  vistsne / vistsne_labels / stream_eval: see test."""
         if visrank and not test_only:
             raise ValueError('visrank can be set to True only if test_only=True')
         if vistsne and not test_only:
             raise ValueError('vistsne can be set to True only if test_only=True')
         _check_rerank(rerank)
+        _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
         eval_args = dict(dist_metric=dist_metric, normalize_feature=normalize_feature, save_dir=save_dir,
-                         use_metric_cuhk03=use_metric_cuhk03, ranks=ranks)
+                         use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, stream_eval=stream_eval)
         if test_only:
             self.test(rerank=rerank, rerank_k1=rerank_k1, rerank_k2=rerank_k2, visrank=visrank,
                       visrank_topk=visrank_topk, vistsne=vistsne, vistsne_labels=vistsne_labels, **eval_args)
@@ -225,7 +241,7 @@ class Engine(object):
     # ---- evaluation ----------------------------------------------------------------------------------------------
     def test(self, dist_metric='euclidean', normalize_feature=False, visrank=False, visrank_topk=10, save_dir='',
              use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7, vistsne=False,
-             vistsne_labels=None):
+             vistsne_labels=None, stream_eval=False):
         """every target dataset in turn (engine.py:287-337); returns the last one's mAP like the reference.
         rerank: False; True = k-reciprocal re-ranking (engine.py:402-406); 'gnn' = GNN re-ranking
         (ieee_amd.rerank.gnn_distmat with rerank_k1, rerank_k2, which the k-reciprocal branch ignores).  The GNN step is
@@ -235,8 +251,12 @@ class Engine(object):
         vistsne: after each report, the feature-space figure that the reference's evaluator draws under its visrank flag
         (engine.py:437-439, 463-490): t-SNE of the three 768-wide slices of the query descriptors into
         <save_dir>/vistsne_<name>/<labels>.jpg (ieee_amd.reidtools.show_points_multimodal).  vistsne_labels: the
-        relabelled identities to draw; None draws random.sample(range(1, 30), 6) like the reference."""
+        relabelled identities to draw; None draws random.sample(range(1, 30), 6) like the reference.
+        stream_eval: the CMC / mAP (Market1501 protocol) without the [Q, G] distance matrix: the gallery's descriptors go by
+        in slabs (ieee_amd.metrics.evaluate_rank_streamed), and the visrank figures come from search_topk.  Same numbers
+        and report.  ValueError with rerank, with use_metric_cuhk03 or over more than one rank."""
         _check_rerank(rerank)
+        _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
         self.set_model_mode('eval')
         mAP = 0.0
         for name, loaders in self.test_loader.items():
@@ -248,7 +268,7 @@ class Engine(object):
                                         visrank_topk=visrank_topk, save_dir=save_dir,
                                         use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, rerank=rerank,
                                         rerank_k1=rerank_k1, rerank_k2=rerank_k2, vistsne=vistsne,
-                                        vistsne_labels=vistsne_labels)
+                                        vistsne_labels=vistsne_labels, stream_eval=stream_eval)
             if self.writer is not None:
                 self.writer.add_scalar('Test/{}/rank1'.format(name), rank1, self.epoch)
                 self.writer.add_scalar('Test/{}/mAP'.format(name), mAP, self.epoch)
@@ -305,9 +325,12 @@ class Engine(object):
     @torch.no_grad()
     def _evaluate(self, dataset_name='', query_loader=None, gallery_loader=None, dist_metric='euclidean',
                   normalize_feature=False, visrank=False, visrank_topk=10, save_dir='', use_metric_cuhk03=False,
-                  ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None):
-        """descriptors -> distance matrix -> CMC / mAP, printed like engine.py:339-441; returns (rank-1, mAP)"""
+                  ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None,
+                  stream_eval=False):
+        """descriptors -> distance matrix -> CMC / mAP, printed like engine.py:339-441; returns (rank-1, mAP).
+        stream_eval: no distance matrix, the gallery goes by in slabs (see test)"""
         _check_rerank(rerank)
+        _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
         if visrank and ddp.world_size() > 1:
             raise RuntimeError('visrank needs the whole distance matrix, which a sharded evaluation over {} ranks never '
                                'forms: run engine.run(test_only=True, visrank=True) in one process on one GPU '
@@ -335,7 +358,11 @@ class Engine(object):
             qf, gf = F.normalize(qf, p=2, dim=1), F.normalize(gf, p=2, dim=1)
         say('Computing distance matrix with metric={} ...'.format(dist_metric))
         sharded = ddp.world_size() > 1 and not use_metric_cuhk03 and not rerank
-        if sharded:     # each rank ranks its slice of the queries against the whole gallery (ieee_amd/dist.py)
+        distmat = None
+        if stream_eval:     # no [Q, G] matrix: two passes over the gallery's descriptors in slabs
+            say('Computing CMC and mAP for {}'.format(dataset_name))
+            cmc, mAP = evaluate_rank_streamed(qf, gf, q_pids, g_pids, q_camids, g_camids, metric=dist_metric)
+        elif sharded:     # each rank ranks its slice of the queries against the whole gallery (ieee_amd/dist.py)
             say('Computing CMC and mAP for {} (queries sharded over {} ranks)'.format(dataset_name, ddp.world_size()))
             cmc, mAP = ddp.sharded_evaluate_rank(qf, gf, q_pids, g_pids, q_camids, g_camids, metric=dist_metric)
         else:
@@ -364,7 +391,8 @@ class Engine(object):
             say('Rank-{:<3}: {:.2%}'.format(r, cmc[r - 1]))     # IndexError when r exceeds the curve, as in the reference
         say('\n')
         if visrank:     # engine.py:423-431 (commented out there): the ranked figures, from the matrix ranked above
-            self._visrank(distmat, dataset_name, query_loader, gallery_loader, visrank_topk, save_dir)
+            self._visrank(distmat, dataset_name, query_loader, gallery_loader, visrank_topk, save_dir,
+                          descriptors=(qf, gf, dist_metric) if stream_eval else None)
         if vistsne:     # engine.py:437-439: what the reference's visrank flag draws
             import random
             from .reidtools import show_points_multimodal
@@ -385,13 +413,23 @@ class Engine(object):
                              '(ieee_amd.data.build_loaders)'.format(name))
         return recs[0], recs[1]
 
-    def _visrank(self, distmat, name, query_loader, gallery_loader, topk, save_dir):
+    def _visrank(self, distmat, name, query_loader, gallery_loader, topk, save_dir, descriptors=None):
+        """descriptors = (qf, gf, metric) instead of a matrix: the ranking comes from search_topk, filtered on the
+        records' labels as visualize_ranked_results filters a matrix"""
         from .reidtools import visualize_ranked_results
         dm = self.datamanager
-        visualize_ranked_results(distmat, self._test_records(name, query_loader, gallery_loader),
+        records = self._test_records(name, query_loader, gallery_loader)
+        indices = None
+        if descriptors is not None:
+            from .metrics import search_topk
+            qf, gf, metric = descriptors
+            lab = lambda recs, col: np.asarray([r[col] for r in recs], dtype=np.int64)
+            indices, _ = search_topk(qf, gf, topk, metric=metric, q_pids=lab(records[0], 1), g_pids=lab(records[1], 1),
+                                     q_camids=lab(records[0], 2), g_camids=lab(records[1], 2))
+        visualize_ranked_results(distmat, records,
                                  getattr(dm, 'data_type', 'image'), width=getattr(dm, 'width', 128),
                                  height=getattr(dm, 'height', 256), save_dir=osp.join(save_dir, 'visrank_' + name),
-                                 topk=topk)
+                                 topk=topk, indices=indices)
 
     # ---- small hooks the reference exposes ------------------------------------------------------------------------
     def compute_loss(self, criterion, outputs, targets):

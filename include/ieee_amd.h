@@ -120,6 +120,53 @@ int ieee_rank_topk_merge(const float* slab, int64_t ldd, int64_t num_q, int64_t 
                          const int32_t* q_pids, const int32_t* slab_g_pids, const int32_t* q_camids,
                          const int32_t* slab_g_camids, int exclude_same_cam, int64_t k, int32_t* state_idx,
                          float* state_dist, void* stream);
+/* ieee_rank_market1501 without the whole [num_q][num_g] matrix: the gallery's distances arrive in column slabs, in two
+ * passes, and the result is the whole-matrix call's -- CMC counts, num_valid_q and every first_pos equal; the AP of a
+ * query with at most 1024 true matches and at most 1024 removed entries equal as bits (and so the AP sum, when every
+ * query is of that kind); the AP of a larger query within nb * 2^-52 (nb true matches: the same nb terms in another
+ * association).  Order: the raw IEEE order of the distances, ties to the smaller GLOBAL gallery index.
+ * The plan comes from the host, which has all four label arrays, as two CSR lists over the queries (device arrays):
+ *   m_off / r_off  int64 [num_q + 1]  segment starts; m_off[num_q] = total_match_keys, r_off[num_q] = total_removed_keys
+ *   m_idx / r_idx  int32 [total]      GLOBAL gallery indices of the query's true matches (same identity, other camera)
+ *                                     and of its removed entries (same identity, same camera), each once
+ *   m_pos / r_pos  int32 [total]      the place of that gallery index in match_columns, the ascending list of the
+ *                                     gallery indices that occur in either list
+ * state: ieee_rank_stream_workspace_bytes(num_q, total_match_keys, total_removed_keys) bytes (device, 8-byte aligned),
+ * the same three numbers in every call: the keys of both lists (uint64), a running count per match key (uint32), ap
+ * and first.  -1 for a negative argument.  The calls of one evaluation, all on one stream:
+ *   collect  slab [num_q][slab_cols] fp32 (row stride ldd >= slab_cols) holds the distances to the gallery entries
+ *            match_columns[col_base ... col_base + slab_cols - 1].  Writes the (distance, global index) key of every
+ *            planned entry whose place falls into the slab.  Every place is collected exactly once, in any order.
+ *   seal     after the last collect: sorts every query's match keys and removed keys ascending, clears the counts.
+ *   count    slab [num_q][slab_g] fp32 (row stride ldd >= slab_g) holds the distances to gallery entries g_base ...
+ *            g_base + slab_g - 1, ALL of them, not only match_columns.  Adds, for every match key, the slab's entries
+ *            with key <= it.  Every gallery column is counted exactly once, in any order (counts add; not checked).
+ *            It reads no labels: removed entries are counted like any entry and leave through their sorted keys -- for a
+ *            query within both 1024 limits here, from the slots they were counted in (what the whole-matrix kernel does
+ *            for such a query), for a larger query in finish.
+ *   finish   after the last count: rank_i = count_i - 1 - #{removed keys < match key i}, AP and first per query in
+ *            ieee_rank_market1501's association, then its summary kernel.  ap [num_q] float64 / first_pos [num_q]
+ *            int32 (device) may be null: the state's own arrays are used.  summary [max_rank + 2] int64 as
+ *            ieee_rank_market1501's; max_rank is NOT clamped to the gallery's size here (the caller does that).
+ *            May be called again (it changes no keys or counts).
+ * 0 <= col_base, col_base + slab_cols < 2^31; 0 <= g_base, g_base + slab_g < 2^31; 1 <= max_rank <= 1024; a state that
+ * is null, misaligned or too small: IEEE_ERR_BAD_ARG before any launch.  num_q == 0, slab_cols == 0 or slab_g == 0 is a
+ * no-op (finish with num_q == 0 writes a zero summary).  No host sync, no atomics on global memory, no floating-point
+ * atomics: the same bits on every call. */
+int64_t ieee_rank_stream_workspace_bytes(int64_t num_q, int64_t total_match_keys, int64_t total_removed_keys);
+int ieee_rank_stream_collect(const float* slab, int64_t ldd, int64_t num_q, int64_t slab_cols, int64_t col_base,
+                             const int64_t* m_off, const int32_t* m_pos, const int32_t* m_idx,
+                             const int64_t* r_off, const int32_t* r_pos, const int32_t* r_idx,
+                             int64_t total_match_keys, int64_t total_removed_keys, void* state,
+                             int64_t state_bytes, void* stream);
+int ieee_rank_stream_seal(int64_t num_q, const int64_t* m_off, const int64_t* r_off, int64_t total_match_keys,
+                          int64_t total_removed_keys, void* state, int64_t state_bytes, void* stream);
+int ieee_rank_stream_count(const float* slab, int64_t ldd, int64_t num_q, int64_t slab_g, int64_t g_base,
+                           const int64_t* m_off, const int64_t* r_off, int64_t total_match_keys,
+                           int64_t total_removed_keys, void* state, int64_t state_bytes, void* stream);
+int ieee_rank_stream_finish(int64_t num_q, const int64_t* m_off, const int64_t* r_off, int64_t total_match_keys,
+                            int64_t total_removed_keys, void* state, int64_t state_bytes, int64_t max_rank,
+                            double* ap, int32_t* first_pos, int64_t* summary, void* stream);
 /* CUHK03 single-gallery-shot protocol, torchreid/metrics/rank.py:24-100 (eval_cuhk03 with the time-id filter): the
  * EXPECTED curve of the protocol's random draw (one gallery image per identity, uniformly), not a 10-sample estimate
  * of it.  distmat [num_q][num_g] fp32 (row stride ldd >= num_g); q_pids / g_pids int32; q_keys / g_keys int32, one
