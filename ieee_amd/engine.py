@@ -32,6 +32,7 @@ from .losses import (CrossEntropyLoss, DeepSupervision, TripletLoss, chunks_shor
 from .meters import AverageMeter, DeferredSummary, MetricMeter
 from .metrics import accuracy, compute_distance_matrix, evaluate_rank, evaluate_rank_streamed
 from .optim import FUSED_OPTIMIZERS, FusedSGD
+from .rerank import _check_formulation
 
 _Entry = namedtuple("_Entry", "model optim sched")
 _SUMMARY_3M = ('loss', 'LossX', 'LossM', 'accR', 'lossR', 'accN', 'lossN', 'accT', 'lossT')
@@ -140,22 +141,24 @@ class Engine(object):
     def run(self, save_dir='log', max_epoch=0, start_epoch=0, print_freq=10, fixbase_epoch=0, open_layers=None,
             start_eval=0, eval_freq=-1, test_only=False, dist_metric='euclidean', normalize_feature=False,
             visrank=False, visrank_topk=10, use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False,
-            rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None, stream_eval=False):
+            rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None, stream_eval=False,
+            rerank_formulation=None):
         """engine.py:126-232.  As in the reference there is NO evaluation or checkpoint after the last epoch (the
         `(epoch + 1) != max_epoch` guard, :216), and re-ranking applies to test_only runs (its docstring, :171-172;
         the in-loop test call does not pass it on, :217-225).  rerank: False, True (k-reciprocal) or 'gnn' (see test;
-        rerank_k1 / rerank_k2 belong to 'gnn' alone).  vistsne / vistsne_labels / stream_eval: see test."""
+        rerank_k1 / rerank_k2 / rerank_formulation belong to 'gnn' alone).  vistsne / vistsne_labels / stream_eval: see test."""
         if visrank and not test_only:
             raise ValueError('visrank can be set to True only if test_only=True')
         if vistsne and not test_only:
             raise ValueError('vistsne can be set to True only if test_only=True')
         _check_rerank(rerank)
+        _check_formulation(rerank_formulation)
         _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
         eval_args = dict(dist_metric=dist_metric, normalize_feature=normalize_feature, save_dir=save_dir,
                          use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, stream_eval=stream_eval)
         if test_only:
-            self.test(rerank=rerank, rerank_k1=rerank_k1, rerank_k2=rerank_k2, visrank=visrank,
-                      visrank_topk=visrank_topk, vistsne=vistsne, vistsne_labels=vistsne_labels, **eval_args)
+            self.test(rerank=rerank, rerank_k1=rerank_k1, rerank_k2=rerank_k2, rerank_formulation=rerank_formulation,
+                      visrank=visrank, visrank_topk=visrank_topk, vistsne=vistsne, vistsne_labels=vistsne_labels, **eval_args)
             return
         began = time.time()
         self.start_epoch, self.max_epoch = start_epoch, max_epoch
@@ -241,10 +244,11 @@ class Engine(object):
     # ---- evaluation ----------------------------------------------------------------------------------------------
     def test(self, dist_metric='euclidean', normalize_feature=False, visrank=False, visrank_topk=10, save_dir='',
              use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7, vistsne=False,
-             vistsne_labels=None, stream_eval=False):
+             vistsne_labels=None, stream_eval=False, rerank_formulation=None):
         """every target dataset in turn (engine.py:287-337); returns the last one's mAP like the reference.
         rerank: False; True = k-reciprocal re-ranking (engine.py:402-406); 'gnn' = GNN re-ranking
-        (ieee_amd.rerank.gnn_distmat with rerank_k1, rerank_k2, which the k-reciprocal branch ignores).  The GNN step is
+        (ieee_amd.rerank.gnn_distmat with rerank_k1, rerank_k2 and formulation=rerank_formulation -- None, 'dense', 'sparse'
+        or 'auto' -- which the k-reciprocal branch ignores; another formulation is a ValueError).  The GNN step is
         always handed L2-normalised descriptors, F.normalize(., p=2, dim=1), whatever dist_metric and normalize_feature
         say: the method ranks by the raw inner product and the reference's driver feeds it normalised rows.  Any other
         string raises ValueError; other values keep their truthiness.
@@ -256,6 +260,7 @@ class Engine(object):
         in slabs (ieee_amd.metrics.evaluate_rank_streamed), and the visrank figures come from search_topk.  Same numbers
         and report.  ValueError with rerank, with use_metric_cuhk03 or over more than one rank."""
         _check_rerank(rerank)
+        _check_formulation(rerank_formulation)
         _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
         self.set_model_mode('eval')
         mAP = 0.0
@@ -268,7 +273,8 @@ class Engine(object):
                                         visrank_topk=visrank_topk, save_dir=save_dir,
                                         use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, rerank=rerank,
                                         rerank_k1=rerank_k1, rerank_k2=rerank_k2, vistsne=vistsne,
-                                        vistsne_labels=vistsne_labels, stream_eval=stream_eval)
+                                        vistsne_labels=vistsne_labels, stream_eval=stream_eval,
+                                        rerank_formulation=rerank_formulation)
             if self.writer is not None:
                 self.writer.add_scalar('Test/{}/rank1'.format(name), rank1, self.epoch)
                 self.writer.add_scalar('Test/{}/mAP'.format(name), mAP, self.epoch)
@@ -326,10 +332,11 @@ class Engine(object):
     def _evaluate(self, dataset_name='', query_loader=None, gallery_loader=None, dist_metric='euclidean',
                   normalize_feature=False, visrank=False, visrank_topk=10, save_dir='', use_metric_cuhk03=False,
                   ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None,
-                  stream_eval=False):
+                  stream_eval=False, rerank_formulation=None):
         """descriptors -> distance matrix -> CMC / mAP, printed like engine.py:339-441; returns (rank-1, mAP).
         stream_eval: no distance matrix, the gallery goes by in slabs (see test)"""
         _check_rerank(rerank)
+        _check_formulation(rerank_formulation)
         _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
         if visrank and ddp.world_size() > 1:
             raise RuntimeError('visrank needs the whole distance matrix, which a sharded evaluation over {} ranks never '
@@ -370,7 +377,8 @@ class Engine(object):
             if rerank == 'gnn':     # GPU-Re-Ranking/gnn_reranking.py on normalised descriptors, as its driver feeds it
                 say('Applying person re-ranking ... (gnn)')
                 from .rerank import gnn_distmat
-                distmat = gnn_distmat(F.normalize(qf, p=2, dim=1), F.normalize(gf, p=2, dim=1), rerank_k1, rerank_k2)
+                distmat = gnn_distmat(F.normalize(qf, p=2, dim=1), F.normalize(gf, p=2, dim=1), rerank_k1, rerank_k2,
+                                      formulation=rerank_formulation)
             elif rerank:  # engine.py:402-406: k-reciprocal re-ranking with the query-query and gallery-gallery matrices
                 say('Applying person re-ranking ...')
                 from .rerank import re_ranking

@@ -79,8 +79,17 @@ def re_ranking(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3, form
 _GNN_PRECISION = {"fp32": 0, "bf16x3": 6, "bf16x2": 3, "f16x2": 2}     # 0, or IEEE_SPLIT_* in include/ieee_amd.h
 
 
-def _gnn(x_q, x_g, k1, k2, precision=None):
-    """ieee_gnn_rerank; returns (distmat, workspace) so that tests can read the intermediates (gnn_layout)"""
+_GNN_FORMULATIONS = (None, "dense", "sparse", "auto")
+
+
+def _check_formulation(formulation):
+    """before a device is needed"""
+    if formulation not in _GNN_FORMULATIONS:
+        raise ValueError("gnn re-ranking: formulation must be None, 'dense', 'sparse' or 'auto', got %r" % (formulation,))
+
+
+def _gnn_inputs(x_q, x_g, precision):
+    """-> (lib, precision, q, g, Q, G, d): the checks and the device copies both formulations start with"""
     lib = _lib.require_gpu()
     if precision is None:
         precision = os.environ.get("IEEE_DISTMAT_PRECISION", "fp32")
@@ -89,19 +98,35 @@ def _gnn(x_q, x_g, k1, k2, precision=None):
     q, g = _dev(x_q), _dev(x_g)
     if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
         raise ValueError("gnn re-ranking: expected X_q [Q, d] and X_g [G, d], got %s and %s" % (tuple(q.shape), tuple(g.shape)))
-    Q, G = q.shape[0], g.shape[0]
     d = (q.shape[1] + 7) // 8 * 8    # kernels move 16-byte chunks: zero columns change no inner product (metrics/distance.py)
+    return lib, precision, q, g, q.shape[0], g.shape[0], d
+
+
+def _gnn_dense_bytes(lib, Q, G, d, k1, k2, precision):
+    """-> (workspace bytes, bytes needed in all, bytes free): the dense formulation's memory check"""
     nbytes = int(lib.ieee_gnn_rerank_workspace_bytes(Q, G, d, int(k1), int(k2), _GNN_PRECISION[precision]))
     if nbytes < 0:
         _lib.check(-1)
-    need = nbytes + (Q * G + (Q + G) * d) * 4
-    free = torch.cuda.mem_get_info()[0]
+    return nbytes, nbytes + (Q * G + (Q + G) * d) * 4, torch.cuda.mem_get_info()[0]
+
+
+def _gnn_features(q, g, d):
+    """one [Q + G, d] array: the scores are then one GEMM"""
+    Q = q.shape[0]
+    x = torch.zeros((Q + g.shape[0], d), dtype=torch.float32, device=q.device)
+    x[:Q, :q.shape[1]] = q
+    x[Q:, :g.shape[1]] = g
+    return x
+
+
+def _gnn(x_q, x_g, k1, k2, precision=None):
+    """ieee_gnn_rerank; returns (distmat, workspace) so that tests can read the intermediates (gnn_layout)"""
+    lib, precision, q, g, Q, G, d = _gnn_inputs(x_q, x_g, precision)
+    nbytes, need, free = _gnn_dense_bytes(lib, Q, G, d, k1, k2, precision)
     if need > free:
         raise RuntimeError("gnn re-ranking is dense: N = Q + G = %d rows need two N x N fp32 work matrices, %d bytes "
                            "with the features and the output, and the device has %d bytes free" % (Q + G, need, free))
-    x = torch.zeros((Q + G, d), dtype=torch.float32, device=q.device)    # one array: the scores are then one GEMM
-    x[:Q, :q.shape[1]] = q
-    x[Q:, :g.shape[1]] = g
+    x = _gnn_features(q, g, d)
     out = torch.empty((Q, G), dtype=torch.float32, device=q.device)
     work = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
     _lib.check(lib.ieee_gnn_rerank(_lib.ptr(x), _lib.ptr(x[Q:]), Q, G, d, int(k1), int(k2), _GNN_PRECISION[precision],
@@ -119,25 +144,215 @@ def gnn_layout(Q, G, d, k1, k2, precision="fp32"):
     return dict(zip(("ld", "rank", "S", "sumsq", "M0", "M1", "rows"), (int(f) for f in fields)))
 
 
-def gnn_distmat(X_q, X_g, k1=26, k2=7, precision=None):
+
+# ---- the sparse formulation (ieee_amd/csrc/gnn_sparse.hip): CSR rows, no (Q+G)^2 and no Q x G allocation --------------
+class _Csr(object):
+    """rowptr int64 [N+1], col int32, val fp32, norm fp32 [N] or None, on the device; nnz as read back"""
+    def __init__(self, rowptr, col, val, norm, nnz):
+        self.rowptr, self.col, self.val, self.norm, self.nnz = rowptr, col, val, norm, nnz
+
+
+def _room(n, dtype, dev):
+    return torch.empty(max(int(n), 1), dtype=dtype, device=dev)     # never a null pointer
+
+
+def _gs_transpose(lib, a, N, r0, r1, scaled, cursor, tptr, trow, tval):
+    _lib.check(lib.ieee_gnn_sparse_transpose(_lib.ptr(a.rowptr), _lib.ptr(a.col), _lib.ptr(a.val),
+                                             _lib.ptr(a.norm if scaled else None), N, r0, r1, _lib.ptr(cursor),
+                                             _lib.ptr(tptr), _lib.ptr(trow), _lib.ptr(tval), trow.numel(), _lib.stream()))
+
+
+def _gs_symmetrise(lib, a, N, scratch, scaled=False, transposed=True):
+    """a / n + (a / n)^T (n = 1 unless scaled); transposed=False: a alone, its rows sorted.  One read-back."""
+    dev = a.col.device
+    tptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    trow, tval = _room(a.nnz if transposed else 0, torch.int32, dev), _room(a.nnz if transposed else 0, torch.float32, dev)
+    if transposed:
+        _gs_transpose(lib, a, N, 0, N, scaled, torch.empty(N, dtype=torch.int32, device=dev), tptr, trow, tval)
+    rowptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    sb = scratch.numel()
+    _lib.check(lib.ieee_gnn_sparse_symmetrise_count(_lib.ptr(a.rowptr), _lib.ptr(a.col), _lib.ptr(tptr), _lib.ptr(trow), N,
+                                                    _lib.ptr(scratch), sb, _lib.ptr(rowptr), _lib.stream()))
+    nnz = int(rowptr[N])
+    col, val = _room(nnz, torch.int32, dev), _room(nnz, torch.float32, dev)
+    norm = torch.empty(N, dtype=torch.float32, device=dev)
+    _lib.check(lib.ieee_gnn_sparse_symmetrise_fill(_lib.ptr(a.rowptr), _lib.ptr(a.col), _lib.ptr(a.val),
+                                                   _lib.ptr(a.norm if scaled else None), _lib.ptr(tptr), _lib.ptr(trow),
+                                                   _lib.ptr(tval), N, _lib.ptr(scratch), sb, _lib.ptr(rowptr),
+                                                   _lib.ptr(col), _lib.ptr(val), _lib.ptr(norm), nnz, _lib.stream()))
+    return _Csr(rowptr, col, val, norm, nnz)
+
+
+def _gs_propagate(lib, a, rank, S, N, k1, k2, scratch):
+    """sum_{j<k2} S[i][j]^2 a[rank[i][j]] with its row norms.  One read-back."""
+    dev = a.col.device
+    rowptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    sb = scratch.numel()
+    _lib.check(lib.ieee_gnn_sparse_propagate_count(_lib.ptr(a.rowptr), _lib.ptr(a.col), _lib.ptr(rank), N, k1, k2,
+                                                   _lib.ptr(scratch), sb, _lib.ptr(rowptr), _lib.stream()))
+    nnz = int(rowptr[N])
+    col, val = _room(nnz, torch.int32, dev), _room(nnz, torch.float32, dev)
+    norm = torch.empty(N, dtype=torch.float32, device=dev)
+    _lib.check(lib.ieee_gnn_sparse_propagate_fill(_lib.ptr(a.rowptr), _lib.ptr(a.col), _lib.ptr(a.val), _lib.ptr(rank),
+                                                  _lib.ptr(S), N, k1, k2, _lib.ptr(scratch), sb, _lib.ptr(rowptr),
+                                                  _lib.ptr(col), _lib.ptr(val), _lib.ptr(norm), nnz, _lib.stream()))
+    return _Csr(rowptr, col, val, norm, nnz)
+
+
+def _check_slab_rows(slab_rows, N):
+    from .metrics.search import default_slab_rows
+    if slab_rows is None:
+        return default_slab_rows(N)
+    if isinstance(slab_rows, bool) or int(slab_rows) != slab_rows or slab_rows < 1:
+        raise ValueError("gnn re-ranking: slab_rows must be a positive integer, got %r" % (slab_rows,))
+    return int(slab_rows)
+
+
+def _gnn_sparse(x_q, x_g, k1, k2, precision=None, slab_rows=None):
+    """steps 1-5 of the sparse formulation -> dict(lib, Q, G, N, slab, rank int32 [N, k1], S fp32 [N, k1] (the negated
+    scores, as the dense workspace keeps them), the final rows rowptr / col / val / norm, and entries: the stored
+    entries of every stage in order).  Four small read-backs, one per sized stage (one when k2 = 1), and one more in
+    _gnn_sparse_ranges."""
+    from .metrics import distance as _dist
+    from .metrics.search import TopKAccumulator
+    lib, precision, q, g, Q, G, d = _gnn_inputs(x_q, x_g, precision)
+    k1, k2 = int(k1), int(k2)
+    N = Q + G
+    sbytes = int(lib.ieee_gnn_sparse_scratch_bytes(Q, G, k1, k2))
+    if sbytes < 0:
+        _lib.check(-1)
+    slab = _check_slab_rows(slab_rows, N)
+    dev = q.device
+    x = _gnn_features(q, g, d)
+    # 1: the k1 best of every row of -X X^T, the columns going by in slabs
+    acc = TopKAccumulator(N, k1, device=dev)
+    width = min(slab, N)
+    buf = torch.empty((N, (width + 3) // 4 * 4), dtype=torch.float32, device=dev)
+    work = torch.empty(_dist._workspace_bytes(lib, N, width, d, torch.float32, precision), dtype=torch.uint8, device=dev)
+    for lo in range(0, N, slab):
+        rows = x[lo:lo + slab]
+        _dist._launch(lib, x, rows, 2, torch.float32, precision, buf, buf.shape[1], work)
+        acc._merge(buf, buf.shape[1], rows.shape[0], None, None)
+    del buf, work, x
+    rank, S = acc._idx, acc._dist
+    # 2-5
+    scratch = torch.zeros(sbytes, dtype=torch.uint8, device=dev)
+    B = _Csr(torch.arange(N + 1, dtype=torch.int64, device=dev) * k1, rank.view(-1),
+             torch.ones(N * k1, dtype=torch.float32, device=dev), None, N * k1)
+    entries = []
+    if k2 == 1:
+        R = _gs_symmetrise(lib, B, N, scratch, transposed=False)
+        entries.append(R.nnz)
+    else:
+        R = _gs_symmetrise(lib, B, N, scratch)
+        entries.append(R.nnz)
+        for last in (False, True):
+            R = _gs_propagate(lib, R, rank, S, N, k1, k2, scratch)
+            entries.append(R.nnz)
+            if not last:
+                R = _gs_symmetrise(lib, R, N, scratch, scaled=True)
+                entries.append(R.nnz)
+    return dict(lib=lib, Q=Q, G=G, N=N, slab=slab, rank=rank, S=S, rowptr=R.rowptr, col=R.col, val=R.val, norm=R.norm,
+                entries=entries)
+
+
+def _gnn_sparse_ranges(st, width):
+    """step 6, range by range: yields (g0, g1, fill), fill(out, ldo) writing 1 - cosine of the range into out (a tensor
+    whose first element is column g0 of row 0, row stride ldo).  The per-range transposes share one set of buffers."""
+    lib, Q, G, N = st["lib"], st["Q"], st["G"], st["N"]
+    R = _Csr(st["rowptr"], st["col"], st["val"], None, None)
+    dev = R.col.device
+    cuts = list(range(0, G, width)) + [G]
+    at = st["rowptr"][torch.tensor([Q + c for c in cuts], dtype=torch.int64, device=dev)].cpu()      # one read-back
+    cap = int((at[1:] - at[:-1]).max())
+    cursor, tptr = torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N + 1, dtype=torch.int64, device=dev)
+    trow, tval = _room(cap, torch.int32, dev), _room(cap, torch.float32, dev)
+    for g0, g1 in zip(cuts[:-1], cuts[1:]):
+        def fill(out, ldo, g0=g0, g1=g1):
+            _gs_transpose(lib, R, N, Q + g0, Q + g1, False, cursor, tptr, trow, tval)
+            _lib.check(lib.ieee_gnn_sparse_cosine(_lib.ptr(R.rowptr), _lib.ptr(R.col), _lib.ptr(R.val), _lib.ptr(st["norm"]),
+                                                  _lib.ptr(tptr), _lib.ptr(trow), _lib.ptr(tval), Q, G, g0, g1,
+                                                  _lib.ptr(out), ldo, _lib.stream()))
+        yield g0, g1, fill
+
+
+def _gnn_sparse_distmat(x_q, x_g, k1, k2, precision=None, slab_rows=None):
+    st = _gnn_sparse(x_q, x_g, k1, k2, precision, slab_rows)
+    Q, G = st["Q"], st["G"]
+    out = torch.empty((Q, G), dtype=torch.float32, device=st["col"].device)
+    for g0, g1, fill in _gnn_sparse_ranges(st, st["slab"]):
+        fill(out[:, g0:], G)
+    return out
+
+
+def _gnn_distmat(X_q, X_g, k1, k2, precision, formulation, slab_rows):
+    _check_formulation(formulation)
+    if formulation == "auto":
+        lib, prec, q, g, Q, G, d = _gnn_inputs(X_q, X_g, precision)
+        _, need, free = _gnn_dense_bytes(lib, Q, G, d, k1, k2, prec)
+        formulation = "dense" if need <= free else "sparse"
+        X_q, X_g = q, g
+    if formulation == "sparse":
+        return _gnn_sparse_distmat(X_q, X_g, k1, k2, precision, slab_rows)
+    return _gnn(X_q, X_g, k1, k2, precision)[0]
+
+
+def gnn_distmat(X_q, X_g, k1=26, k2=7, precision=None, formulation=None, slab_rows=None):
     """GNN re-ranking as a [Q, G] fp32 distance matrix, 1 - similarity, so that evaluate_rank, rank_topk and
     visualize_ranked_results take it like any other: a CUDA tensor when X_q is one, else a numpy array.  The features
     are used as they are (plain inner products, as in the reference): hand in L2-normalised rows, as the reference's
     driver does (main.py) -- on rows that are not normalised the raw inner product is a poor first ranking.  Defaults
     are that driver's Market-1501 values.  Where the reference leaves the result open: ties are broken by the smaller
     index, and a row whose propagated vector is all zero (e.g. an all-zero feature row) has similarity 0 to everything,
-    not the reference's NaN.  precision: as in metrics.distance (fp32, or a split scheme for the two GEMMs).  Dense:
-    two (Q+G)^2 fp32 work matrices; raises RuntimeError when the device has not that much free."""
-    out, _ = _gnn(X_q, X_g, k1, k2, precision)
+    not the reference's NaN.  precision: as in metrics.distance (fp32, or a split scheme for the GEMMs).
+    formulation: None or 'dense' -- two (Q+G)^2 fp32 work matrices, RuntimeError when the device has not that much
+    free; 'sparse' -- the same algorithm on CSR rows (ieee_gnn_sparse_*), no (Q+G)^2 allocation, the same result within
+    rounding (its sums skip the dense form's zero terms and its final product runs in another order); 'auto' -- dense
+    when that memory check passes, else sparse.  slab_rows (sparse only): the columns of the score slab [Q+G, slab_rows]
+    of the first ranking and the width of the final product's gallery ranges, metrics.search.default_slab_rows(Q+G) by
+    default; the result does not depend on it."""
+    out = _gnn_distmat(X_q, X_g, k1, k2, precision, formulation, slab_rows)
     if isinstance(X_q, torch.Tensor) and X_q.is_cuda:
         return out
     return out.cpu().numpy()
 
 
-def gnn_reranking(X_q, X_g, k1, k2):
+def gnn_reranking(X_q, X_g, k1, k2, formulation=None):
     """the reference's gnn_reranking(X_q, X_g, k1, k2) (GPU-Re-Ranking/gnn_reranking.py:27-59): L, an integer numpy
     array [Q, G], row i the gallery indices of query i best first (a stable sort of gnn_distmat's rows: equal
     similarities in index order).  CPU or CUDA tensors, or numpy arrays.  See gnn_distmat for what is defined here
-    that the reference leaves open (ties; zero rows give similarity 0, not NaN)."""
-    out, _ = _gnn(X_q, X_g, k1, k2)
+    that the reference leaves open (ties; zero rows give similarity 0, not NaN) and for formulation."""
+    out = _gnn_distmat(X_q, X_g, k1, k2, None, formulation, None)
     return torch.sort(out, dim=1, stable=True)[1].cpu().numpy()
+
+
+def gnn_search_topk(X_q, X_g, k, k1=26, k2=7, q_pids=None, g_pids=None, q_camids=None, g_camids=None, precision=None,
+                    slab_rows=None):
+    """The k nearest kept gallery entries of every query under GNN re-ranking, without the [Q, G] matrix:
+    -> (indices int64 [Q, k], distances fp32 [Q, k]) on the device, what rank_topk(gnn_distmat(X_q, X_g, k1, k2,
+    formulation='sparse'), k, ...) lists, bit for bit.  The sparse rows are built once; the final product goes gallery
+    range by gallery range (slab_rows wide) into one reused [Q, slab_rows] buffer that ieee_rank_topk_merge folds into
+    the running lists.  Labels as in search_topk: all four of q_pids, g_pids, q_camids, g_camids (an entry with the
+    query's identity and camera is not kept) or none; -1 / +inf where a row has fewer than k kept entries."""
+    from .metrics.search import TopKAccumulator, _check_k, _host_labels, _on
+    who = "gnn_search_topk"
+    k = _check_k(k, who)
+    labels = (q_pids, g_pids, q_camids, g_camids)
+    given = sum(v is not None for v in labels)
+    if given not in (0, 4):
+        raise ValueError("%s: give all four of q_pids, g_pids, q_camids, g_camids, or none (got %d)" % (who, given))
+    if given:
+        Q, G = int(np.shape(X_q)[0]), int(np.shape(X_g)[0])
+        q_pids, q_camids = _host_labels(q_pids, "q_pids", Q, who), _host_labels(q_camids, "q_camids", Q, who)
+        g_pids, g_camids = _host_labels(g_pids, "g_pids", G, who), _host_labels(g_camids, "g_camids", G, who)
+    st = _gnn_sparse(X_q, X_g, k1, k2, precision, slab_rows)
+    Q, G, dev = st["Q"], st["G"], st["col"].device
+    acc = TopKAccumulator(Q, k, q_pids if given else None, q_camids if given else None, device=dev)
+    if given:
+        g_pids, g_camids = _on(g_pids, dev), _on(g_camids, dev)
+    width = min(st["slab"], G)
+    buf = torch.empty((Q, (width + 3) // 4 * 4), dtype=torch.float32, device=dev)
+    for g0, g1, fill in _gnn_sparse_ranges(st, width):
+        fill(buf, buf.shape[1])
+        acc._merge(buf, buf.shape[1], g1 - g0, g_pids[g0:g1] if given else None, g_camids[g0:g1] if given else None)
+    return acc.result()

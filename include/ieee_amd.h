@@ -715,6 +715,57 @@ int ieee_gnn_rerank(const float* xq, const float* xg, int64_t Q, int64_t G, int6
  * rows fed the final product (M1, the unnormalised second round; M0 = the binary B when k2 = 1)}. */
 int ieee_gnn_rerank_layout(int64_t Q, int64_t G, int64_t d, int64_t k1, int64_t k2, int precision, int64_t* fields);
 
+/* ---- GNN re-ranking on sparse rows: the algorithm of ieee_gnn_rerank with only the structural non-zeros stored, and
+ * nothing of size N x N or Q x G allocated (N = Q + G).  A sparse matrix here is CSR: rowptr [N+1] int64, col int32
+ * (strictly ascending inside a row), val fp32; every stage that makes one comes as a _count call, which writes the
+ * output's rowptr (rowptr[N] = its number of entries, which the caller reads back to allocate col and val), and a _fill
+ * call.  The caller owns all memory and runs the stages in this order (ieee_amd/rerank.py::_gnn_sparse):
+ *   rank, S [N][k1] from ieee_rank_topk_merge over column slabs of -X_u X_u^T (metric 2), as ieee_gnn_rerank's;
+ *   B = the CSR view of rank (rowptr[i] = i k1, col = rank, val = 1: the one input whose rows need not be sorted);
+ *   M0 = symmetrise(B, transpose(B));  M1 = propagate(M0);  M0' = symmetrise(M1, transpose(M1), norms of M1);
+ *   R = propagate(M0'), with its row norms;  per gallery range [g0, g1): T = transpose of rows Q+g0 .. Q+g1-1 of R,
+ *   then ieee_gnn_sparse_cosine.  k2 = 1: R = symmetrise(B, an empty transposed side), i.e. B with sorted rows.
+ * No floating-point atomics: every sum has a fixed order and two calls give the same bits.  Everything on `stream`, no
+ * host sync.  Bad arguments (null pointers, the bounds below) give IEEE_ERR_BAD_ARG before any launch.
+ *
+ * scratch: the work rows of symmetrise and propagate, ieee_gnn_sparse_scratch_bytes(Q, G, k1, k2) bytes (at most 512
+ * rows of N floats and N bits), ALL ZERO before the first call; every call leaves it all zero again.  The function
+ * checks the whole call's bounds, those of ieee_gnn_rerank: Q, G >= 1 and < 2^30, 1 <= k2 <= k1 <= min(1024, N); it
+ * returns -1 and sets the error text otherwise. */
+int64_t ieee_gnn_sparse_scratch_bytes(int64_t Q, int64_t G, int64_t k1, int64_t k2);
+/* Transpose of rows [r0, r1) of a CSR matrix with N rows and N columns: list c = tptr[c] .. tptr[c+1] holds, for
+ * every entry (r, c, v) of those rows, trow = r and tval = v / max(norm[r], 1e-12) (v itself when norm is null), in no
+ * particular order (the rows of one list are distinct).  tptr [N+1] int64, cursor [N] int32 (work), trow / tval with
+ * room for cap entries: rowptr[r1] - rowptr[r0] are written, and nothing beyond cap. */
+int ieee_gnn_sparse_transpose(const int64_t* rowptr, const int32_t* col, const float* val, const float* norm, int64_t N,
+                              int64_t r0, int64_t r1, int32_t* cursor, int64_t* tptr, int32_t* trow, float* tval,
+                              int64_t cap, void* stream);
+/* out = A / n + (A / n)^T, n_r = max(norm[r], 1e-12) (n = 1 when norm is null): row i is the union of row i of A,
+ * scaled, and list i of the (already scaled) transpose from ieee_gnn_sparse_transpose; a column both sides hold gets
+ * their sum.  The rows of A need not be sorted; the output's are.  out_norm (may be null) receives the output's row
+ * norms.  Nothing is written beyond cap entries. */
+int ieee_gnn_sparse_symmetrise_count(const int64_t* rowptr, const int32_t* col, const int64_t* tptr, const int32_t* trow,
+                                     int64_t N, void* scratch, int64_t scratch_bytes, int64_t* out_rowptr, void* stream);
+int ieee_gnn_sparse_symmetrise_fill(const int64_t* rowptr, const int32_t* col, const float* val, const float* norm,
+                                    const int64_t* tptr, const int32_t* trow, const float* tval, int64_t N, void* scratch,
+                                    int64_t scratch_bytes, const int64_t* out_rowptr, int32_t* out_col, float* out_val,
+                                    float* out_norm, int64_t cap, void* stream);
+/* out[i] = sum_{j < k2} S[i][j]^2 A[rank[i][j]], per column in ascending j with one fma per term (the dense
+ * gnn_propagate arithmetic without its zero terms); out_norm[i] = |out[i]| (not clamped).  Source rows of any length. */
+int ieee_gnn_sparse_propagate_count(const int64_t* rowptr, const int32_t* col, const int32_t* rank, int64_t N, int64_t k1,
+                                    int64_t k2, void* scratch, int64_t scratch_bytes, int64_t* out_rowptr, void* stream);
+int ieee_gnn_sparse_propagate_fill(const int64_t* rowptr, const int32_t* col, const float* val, const int32_t* rank,
+                                   const float* S, int64_t N, int64_t k1, int64_t k2, void* scratch, int64_t scratch_bytes,
+                                   const int64_t* out_rowptr, int32_t* out_col, float* out_val, float* out_norm,
+                                   int64_t cap, void* stream);
+/* out[q][g - g0] = 1 - <R_q, R_{Q+g}> / (max(norm[q], 1e-12) max(norm[Q+g], 1e-12)) for q < Q, g0 <= g < g1: `out`
+ * points at the range's first column, row stride ldo >= g1 - g0.  (tptr, trow, tval) is the transpose of rows Q+g0 ..
+ * Q+g1-1 of R with norm null.  The sum of one pair runs over the shared columns in ascending order whatever the range,
+ * so the bits do not depend on how the gallery is cut; a pair without a shared column, and a zero row, give exactly 1. */
+int ieee_gnn_sparse_cosine(const int64_t* rowptr, const int32_t* col, const float* val, const float* norm,
+                           const int64_t* tptr, const int32_t* trow, const float* tval, int64_t Q, int64_t G, int64_t g0,
+                           int64_t g1, float* out, int64_t ldo, void* stream);
+
 /* ---- descriptor t-SNE (torchreid/engine/engine.py:463-490, showPointMultiModal) ---------------------------------- */
 /* Exact (dense, O(n^2)) t-SNE in 2 output dimensions, Student-t degree of freedom 1, what the reference gets from
  * sklearn.manifold.TSNE(n_components=2).  `batch` independent problems of the same n run per call, on a grid axis (the
