@@ -9,26 +9,19 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ._stream import device_matrix, host_labels, on_device
 
 
 def _i32(x, name, device):
-    x = np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x)
-    if x.size and (x.max() > np.iinfo(np.int32).max or x.min() < np.iinfo(np.int32).min):
-        raise ValueError("%s does not fit int32" % name)
-    return torch.from_numpy(np.ascontiguousarray(x.astype(np.int32))).to(device)
+    """labels as a flat int32 array on the device, their range checked"""
+    return on_device(host_labels(x, name, None, None), device)
 
 
 def rank_counts(distmat, q_pids, g_pids, q_camids, g_camids, max_rank):
     """the device part of eval_market1501: returns (cmc_counts int64[max_rank], num_valid_q, AP sum) of the given
     queries -- additive over disjoint query sets, which is what a query-sharded evaluation all-reduces"""
     lib = _lib.require_gpu()
-    if isinstance(distmat, torch.Tensor):
-        d = distmat if distmat.is_cuda else distmat.cuda()
-    else:
-        d = torch.from_numpy(np.ascontiguousarray(distmat, dtype=np.float32)).cuda()
-    d = d.to(torch.float32)
-    if d.stride(-1) != 1:
-        d = d.contiguous()
+    d, ldd = device_matrix(distmat)
     num_q, num_g = d.shape
     dev = d.device
     qp, gp = _i32(q_pids, "q_pids", dev), _i32(g_pids, "g_pids", dev)
@@ -40,7 +33,7 @@ def rank_counts(distmat, q_pids, g_pids, q_camids, g_camids, max_rank):
     first = torch.empty(num_q, dtype=torch.int32, device=dev)
     summary = torch.empty(max_rank + 2, dtype=torch.int64, device=dev)
     work = torch.empty(lib.ieee_rank_workspace_bytes(num_g), dtype=torch.uint8, device=dev)
-    _lib.check(lib.ieee_rank_market1501_ws(_lib.ptr(d), d.stride(0), num_q, num_g, _lib.ptr(qp), _lib.ptr(gp),
+    _lib.check(lib.ieee_rank_market1501_ws(_lib.ptr(d), ldd, num_q, num_g, _lib.ptr(qp), _lib.ptr(gp),
                                            _lib.ptr(qc), _lib.ptr(gc), max_rank, _lib.ptr(ap), _lib.ptr(first),
                                            _lib.ptr(summary), _lib.ptr(work), work.numel(), _lib.stream()))
     s = summary.cpu().numpy()          # the evaluator's single read-back (22 words)
@@ -87,13 +80,7 @@ def cuhk03_sums(distmat, q_pids, g_pids, q_camids, g_camids, q_timeids, g_timeid
     curves float64[num_q][max_rank] (zeros for a skipped query) and APs float64[num_q] (-1 when skipped) as device
     tensors, for tests and tools."""
     lib = _lib.require_gpu()
-    if isinstance(distmat, torch.Tensor):
-        d = distmat if distmat.is_cuda else distmat.cuda()
-    else:
-        d = torch.from_numpy(np.ascontiguousarray(distmat, dtype=np.float32)).cuda()
-    d = d.to(torch.float32)
-    if d.stride(-1) != 1:
-        d = d.contiguous()
+    d, ldd = device_matrix(distmat)
     num_q, num_g = d.shape
     dev = d.device
     qk, gk = fold_keys(q_camids, g_camids, q_timeids, g_timeids)
@@ -106,7 +93,7 @@ def cuhk03_sums(distmat, q_pids, g_pids, q_camids, g_camids, q_timeids, g_timeid
         return np.zeros(max_rank, dtype=np.float64), 0.0, 0.0, cmc, ap
     summary = torch.empty(max_rank + 2, dtype=torch.float64, device=dev)
     work = torch.empty(lib.ieee_rank_cuhk03_workspace_bytes(num_g), dtype=torch.uint8, device=dev)
-    _lib.check(lib.ieee_rank_cuhk03(_lib.ptr(d), d.stride(0), num_q, num_g, _lib.ptr(qp), _lib.ptr(gp), _lib.ptr(qk),
+    _lib.check(lib.ieee_rank_cuhk03(_lib.ptr(d), ldd, num_q, num_g, _lib.ptr(qp), _lib.ptr(gp), _lib.ptr(qk),
                                     _lib.ptr(gk), max_rank, _lib.ptr(cmc), _lib.ptr(ap), _lib.ptr(summary),
                                     _lib.ptr(work), work.numel(), _lib.stream()))
     s = summary.cpu().numpy()          # the single read-back

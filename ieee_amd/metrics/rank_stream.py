@@ -15,10 +15,11 @@ import torch
 
 from .. import _lib
 from . import distance as _dist
+from ._stream import (SlabDistances, check_device, check_metric, check_precision, check_query, check_slab, count_rows,
+                      device_matrix, host_labels, on_device, walk)
 from .rank import finish_counts
-from .search import _METRIC_ID, _host_labels, _on, default_slab_rows
 
-_INDEX_LIMIT = 1 << 31
+RANK_STREAM_INDEX_LIMIT = 1 << 31   # ieee_rank_stream_collect / _count refuse a slab that ends at or beyond this index
 MAX_RANK_LIMIT = 1024               # rank_finalize_kernel's histogram
 
 
@@ -70,17 +71,15 @@ class RankAccumulator(object):
 
     def __init__(self, q_pids, q_camids, g_pids, g_camids, max_rank=20, device=None):
         who = "RankAccumulator"
-        q_pids = _host_labels(q_pids, "q_pids", None, who)
-        q_camids = _host_labels(q_camids, "q_camids", q_pids.size, who)
-        g_pids = _host_labels(g_pids, "g_pids", None, who)
-        g_camids = _host_labels(g_camids, "g_camids", g_pids.size, who)
+        q_pids = host_labels(q_pids, "q_pids", None, who)
+        q_camids = host_labels(q_camids, "q_camids", q_pids.size, who)
+        g_pids = host_labels(g_pids, "g_pids", None, who)
+        g_camids = host_labels(g_camids, "g_camids", g_pids.size, who)
         if isinstance(max_rank, bool) or int(max_rank) != max_rank or not 1 <= int(max_rank) <= MAX_RANK_LIMIT:
             raise ValueError("%s: max_rank must be an integer in [1, %d], got %r" % (who, MAX_RANK_LIMIT, max_rank))
-        if g_pids.size >= _INDEX_LIMIT or q_pids.size >= _INDEX_LIMIT:
-            raise ValueError("%s: more than %d entries" % (who, _INDEX_LIMIT - 1))
-        self.device = torch.device("cuda" if device is None else device)
-        if self.device.type != "cuda":
-            raise ValueError("%s: device must be a CUDA device, got %s" % (who, self.device))
+        if g_pids.size >= RANK_STREAM_INDEX_LIMIT or q_pids.size >= RANK_STREAM_INDEX_LIMIT:
+            raise ValueError("%s: more than %d entries" % (who, RANK_STREAM_INDEX_LIMIT - 1))
+        self.device = check_device(device, who)
         self.num_q, self.num_g = int(q_pids.size), int(g_pids.size)
         self.max_rank = max(1, min(int(max_rank), self.num_g))      # rank.py:110-115
         self.plan = RankPlan(q_pids, q_camids, g_pids, g_camids)
@@ -98,8 +97,8 @@ class RankAccumulator(object):
             tm, tr = int(p.m_off[-1]), int(p.r_off[-1])
             nbytes = int(lib.ieee_rank_stream_workspace_bytes(self.num_q, tm, tr))
             self._dev = dict(lib=lib, tm=tm, tr=tr, state=torch.empty(nbytes, dtype=torch.uint8, device=dev),
-                             m_off=_on(p.m_off, dev), m_pos=_on(p.m_pos, dev), m_idx=_on(p.m_idx, dev),
-                             r_off=_on(p.r_off, dev), r_pos=_on(p.r_pos, dev), r_idx=_on(p.r_idx, dev),
+                             **{name: on_device(getattr(p, name), dev)
+                                for name in ("m_off", "m_pos", "m_idx", "r_off", "r_pos", "r_idx")},
                              ap=torch.empty(self.num_q, dtype=torch.float64, device=dev),
                              first=torch.empty(self.num_q, dtype=torch.int32, device=dev))
         return self._dev
@@ -111,17 +110,6 @@ class RankAccumulator(object):
                              % (who, self.num_q, tuple(getattr(dist_slab, "shape", ()))))
         return int(dist_slab.shape[1])
 
-    def _to_device(self, dist_slab, n):
-        if isinstance(dist_slab, torch.Tensor):
-            d = dist_slab.to(self.device)
-        else:
-            d = np.ascontiguousarray(dist_slab, dtype=np.float32)
-            d = torch.from_numpy(d if d.flags.writeable else d.copy()).to(self.device)
-        d = d.to(torch.float32)
-        if d.stride(-1) != 1 or d.stride(0) < n:
-            d = d.contiguous()
-        return d, max(d.stride(0), n)
-
     # ---- pass 1
     def collect(self, dist_slab):
         who = "RankAccumulator.collect"
@@ -132,8 +120,7 @@ class RankAccumulator(object):
             raise ValueError("%s: %d + %d columns run past the %d match columns"
                              % (who, self.num_collected, n, self.match_columns.size))
         if self.num_q and n:
-            d, ldd = self._to_device(dist_slab, n)
-            self._collect(d, ldd, n)
+            self._collect(*device_matrix(dist_slab, self.device, n), n)
         else:
             self.num_collected += n
 
@@ -169,8 +156,7 @@ class RankAccumulator(object):
         g_base = int(g_base)
         self._claim(g_base, n, who)
         if self.num_q and n and self.match_columns.size:
-            d, ldd = self._to_device(dist_slab, n)
-            self._count(d, ldd, n, g_base)
+            self._count(*device_matrix(dist_slab, self.device, n), n, g_base)
 
     def _claim(self, g_base, n, who="RankAccumulator.count"):
         if n == 0:
@@ -221,63 +207,33 @@ class RankAccumulator(object):
         return s["ap"].clone(), s["first"].clone()
 
 
-def _gallery_pieces(gallery, dim, who):
-    if isinstance(gallery, torch.Tensor):
-        gallery = (gallery,)
-    if not isinstance(gallery, (list, tuple)):
+def _streamed(who, query, gallery, q_pids, g_pids, q_camids, g_camids, max_rank, metric, slab, precision, clamp=False):
+    """both passes over the gallery's descriptors -> the RankAccumulator, every column counted.  clamp: max_rank is
+    eval_market1501's, at most the gallery's size (rank.py:110-115)"""
+    metric_id = check_metric(metric)
+    check_precision(precision)
+    Q, dim = check_query(query, who)
+    pieces = (gallery,) if isinstance(gallery, torch.Tensor) else gallery
+    if not isinstance(pieces, (list, tuple)):
         raise ValueError("%s: the gallery is walked twice, so it must be a [G, d] tensor or a list / tuple of [g, d] "
                          "tensors; a one-shot iterator (got %s) cannot be walked again" % (who, type(gallery).__name__))
-    for piece in gallery:
-        if not isinstance(piece, torch.Tensor) or piece.dim() != 2 or piece.shape[1] != dim:
-            raise ValueError("%s: the gallery and every piece of it must be a [g, %d] tensor, got %s"
-                             % (who, dim, tuple(piece.shape) if isinstance(piece, torch.Tensor) else type(piece).__name__))
-    return gallery
-
-
-def _streamed(who, query, gallery, q_pids, g_pids, q_camids, g_camids, max_rank, metric, slab, precision):
-    """both passes over the gallery's descriptors -> the RankAccumulator, every column counted"""
-    if metric not in _METRIC_ID:
-        raise ValueError('Unknown distance metric: {}. Please choose either "euclidean" or "cosine"'.format(metric))
-    if precision is not None and precision not in _dist.PRECISIONS:
-        raise ValueError("Unknown distmat precision: {}. Choose one of {}".format(precision, _dist.PRECISIONS))
-    if not isinstance(query, torch.Tensor) or query.dim() != 2:
-        raise ValueError("%s: query must be a [Q, d] tensor, got %s"
-                         % (who, tuple(query.shape) if isinstance(query, torch.Tensor) else type(query).__name__))
-    Q, dim = query.shape
-    pieces = _gallery_pieces(gallery, dim, who)
-    G = sum(int(piece.shape[0]) for piece in pieces)
-    if slab is None:
-        slab = default_slab_rows(Q)
-    if isinstance(slab, bool) or int(slab) != slab or slab < 1:
-        raise ValueError("%s: slab must be a positive integer, got %r" % (who, slab))
-    slab = int(slab)
-    q_pids = _host_labels(q_pids, "q_pids", Q, who)
-    g_pids = _host_labels(g_pids, "g_pids", G, who)
+    G = count_rows(pieces, dim, who)
+    if clamp and G < max_rank:
+        max_rank = G
+        print('Note: number of gallery samples is quite small, got {}'.format(G))
+        if max_rank < 1:
+            raise ValueError("%s: the gallery is empty" % who)
+    slab = check_slab(slab, Q, who)
+    q_pids = host_labels(q_pids, "q_pids", Q, who)
+    g_pids = host_labels(g_pids, "g_pids", G, who)
     acc = RankAccumulator(q_pids, q_camids, g_pids, g_camids, max_rank)
     if Q == 0 or G == 0 or acc.match_columns.size == 0:      # nothing to rank: every query is skipped
         acc.num_collected = acc.match_columns.size
         acc.seal()
         acc._claim(0, G)
         return acc
-    lib, dev = _lib.require_gpu(), acc.device
     precision, cdt = _dist._resolve(precision, query.dtype)
-    metric_id = _METRIC_ID[metric]
-    q = _dist._pad8(query.detach().to(dev).to(cdt).contiguous())
-    bufs = {"buf": None, "work": None}
-
-    def distances(rows):
-        """the [Q, n] distances to `rows` in the one reused buffer -> (buffer, its row stride)"""
-        n = rows.shape[0]
-        if bufs["buf"] is None or bufs["buf"].shape[1] < n:   # as wide as the widest slab (rows stay 16-byte aligned)
-            bufs["buf"] = None                                # the narrower one goes before its successor comes
-            bufs["buf"] = torch.empty((Q, (n + 3) // 4 * 4), dtype=torch.float32, device=dev)
-        need = _dist._workspace_bytes(lib, Q, n, q.shape[1], cdt, precision)
-        if bufs["work"] is None or bufs["work"].numel() < need:
-            bufs["work"] = None
-            bufs["work"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        _dist._launch(lib, q, rows, metric_id, cdt, precision, bufs["buf"], bufs["buf"].shape[1], bufs["work"])
-        return bufs["buf"], bufs["buf"].shape[1]
-
+    distances = SlabDistances(_lib.require_gpu(), query, metric_id, cdt, precision, acc.device)
     # ---- pass 1: the rows of match_columns, piece by piece
     mc, base = acc.match_columns, 0
     for piece in pieces:
@@ -289,20 +245,13 @@ def _streamed(who, query, gallery, q_pids, g_pids, q_camids, g_camids, max_rank,
                 rows = piece[int(pick[0]):int(pick[-1]) + 1]   # distractors): a view, nothing is gathered
             else:
                 rows = piece.detach().index_select(0, torch.from_numpy(pick).to(piece.device))
-            rows = _dist._pad8(rows.detach().to(dev).to(cdt).contiguous())
-            acc._collect(*distances(rows), rows.shape[0])      # no name is bound to the buffer: a wider one replaces it
-
+            acc._collect(*distances.stage(rows))
         base += g
     acc.seal()
     # ---- pass 2: every gallery row, in slabs
-    base, rows = 0, None
-    for piece in pieces:
-        for lo in range(0, int(piece.shape[0]), slab):
-            rows = None
-            rows = _dist._pad8(piece[lo:lo + slab].detach().to(dev).to(cdt).contiguous())
-            acc._claim(base + lo, rows.shape[0])
-            acc._count(*distances(rows), rows.shape[0], base + lo)
-        base += int(piece.shape[0])
+    for base, rows in walk(pieces, slab, dim, who):
+        acc._claim(base, rows.shape[0])
+        acc._count(*distances.stage(rows), base)
     return acc
 
 
@@ -326,15 +275,6 @@ def evaluate_rank_streamed(query, gallery, q_pids, g_pids, q_camids, g_camids, m
     gathers the rows whose identity occurs among the queries; pass 2 cuts every piece into slabs of at most `slab` rows
     (default_slab_rows(Q) by default); only one slab of a host piece is on the device at a time.  metric and precision
     are compute_distance_matrix's."""
-    who = "evaluate_rank_streamed"
-    if not isinstance(gallery, torch.Tensor) and isinstance(gallery, (list, tuple)):
-        num_g = sum(int(p.shape[0]) for p in gallery if isinstance(p, torch.Tensor))
-    else:
-        num_g = int(gallery.shape[0]) if isinstance(gallery, torch.Tensor) else None
-    if num_g is not None and num_g < max_rank:
-        max_rank = num_g
-        print('Note: number of gallery samples is quite small, got {}'.format(num_g))
-        if max_rank < 1:
-            raise ValueError("%s: the gallery is empty" % who)
-    acc = _streamed(who, query, gallery, q_pids, g_pids, q_camids, g_camids, max_rank, metric, slab, precision)
+    acc = _streamed("evaluate_rank_streamed", query, gallery, q_pids, g_pids, q_camids, g_camids, max_rank, metric, slab,
+                    precision, clamp=True)
     return finish_counts(*acc.result())

@@ -8,14 +8,14 @@ import numpy as np
 import torch
 
 from . import _lib
+from .metrics._stream import (SlabDistances, check_k, check_labels_all_or_none, check_slab, device_matrix, host_labels,
+                              on_device)
+from .metrics.search import TopKAccumulator
 
 
 def _dev(x):
-    if isinstance(x, torch.Tensor):
-        t = x if x.is_cuda else x.cuda()
-    else:
-        t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
-    return t.to(torch.float32).contiguous()
+    """device_matrix with the rows back to back: the re-ranking kernels take no row stride"""
+    return device_matrix(x)[0].contiguous()
 
 
 DENSE_LIMIT = 46000      # the dense formulation holds three (Q+G)^2 fp32 work matrices: Q+G below this only
@@ -199,42 +199,27 @@ def _gs_propagate(lib, a, rank, S, N, k1, k2, scratch):
     return _Csr(rowptr, col, val, norm, nnz)
 
 
-def _check_slab_rows(slab_rows, N):
-    from .metrics.search import default_slab_rows
-    if slab_rows is None:
-        return default_slab_rows(N)
-    if isinstance(slab_rows, bool) or int(slab_rows) != slab_rows or slab_rows < 1:
-        raise ValueError("gnn re-ranking: slab_rows must be a positive integer, got %r" % (slab_rows,))
-    return int(slab_rows)
-
-
 def _gnn_sparse(x_q, x_g, k1, k2, precision=None, slab_rows=None):
     """steps 1-5 of the sparse formulation -> dict(lib, Q, G, N, slab, rank int32 [N, k1], S fp32 [N, k1] (the negated
     scores, as the dense workspace keeps them), the final rows rowptr / col / val / norm, and entries: the stored
     entries of every stage in order).  Four small read-backs, one per sized stage (one when k2 = 1), and one more in
     _gnn_sparse_ranges."""
-    from .metrics import distance as _dist
-    from .metrics.search import TopKAccumulator
     lib, precision, q, g, Q, G, d = _gnn_inputs(x_q, x_g, precision)
     k1, k2 = int(k1), int(k2)
     N = Q + G
     sbytes = int(lib.ieee_gnn_sparse_scratch_bytes(Q, G, k1, k2))
     if sbytes < 0:
         _lib.check(-1)
-    slab = _check_slab_rows(slab_rows, N)
+    slab = check_slab(slab_rows, N, "gnn re-ranking", "slab_rows")
     dev = q.device
     x = _gnn_features(q, g, d)
-    # 1: the k1 best of every row of -X X^T, the columns going by in slabs
+    # 1: the k1 best of every row of -X X^T (metric id 2), the columns going by in slabs; the first slab is the widest
     acc = TopKAccumulator(N, k1, device=dev)
-    width = min(slab, N)
-    buf = torch.empty((N, (width + 3) // 4 * 4), dtype=torch.float32, device=dev)
-    work = torch.empty(_dist._workspace_bytes(lib, N, width, d, torch.float32, precision), dtype=torch.uint8, device=dev)
+    scores = SlabDistances(lib, x, 2, torch.float32, precision, dev)
     for lo in range(0, N, slab):
-        rows = x[lo:lo + slab]
-        _dist._launch(lib, x, rows, 2, torch.float32, precision, buf, buf.shape[1], work)
-        acc._merge(buf, buf.shape[1], rows.shape[0], None, None)
-    del buf, work, x
-    rank, S = acc._idx, acc._dist
+        acc.merge(*scores.stage(x[lo:lo + slab]))
+    del scores, x                                   # the slab buffer, its workspace and the features go before steps 2-5
+    rank, S = acc.state()
     # 2-5
     scratch = torch.zeros(sbytes, dtype=torch.uint8, device=dev)
     B = _Csr(torch.arange(N + 1, dtype=torch.int64, device=dev) * k1, rank.view(-1),
@@ -334,25 +319,21 @@ def gnn_search_topk(X_q, X_g, k, k1=26, k2=7, q_pids=None, g_pids=None, q_camids
     range by gallery range (slab_rows wide) into one reused [Q, slab_rows] buffer that ieee_rank_topk_merge folds into
     the running lists.  Labels as in search_topk: all four of q_pids, g_pids, q_camids, g_camids (an entry with the
     query's identity and camera is not kept) or none; -1 / +inf where a row has fewer than k kept entries."""
-    from .metrics.search import TopKAccumulator, _check_k, _host_labels, _on
     who = "gnn_search_topk"
-    k = _check_k(k, who)
-    labels = (q_pids, g_pids, q_camids, g_camids)
-    given = sum(v is not None for v in labels)
-    if given not in (0, 4):
-        raise ValueError("%s: give all four of q_pids, g_pids, q_camids, g_camids, or none (got %d)" % (who, given))
+    k = check_k(k, who)
+    given = check_labels_all_or_none(q_pids, g_pids, q_camids, g_camids, who)
     if given:
         Q, G = int(np.shape(X_q)[0]), int(np.shape(X_g)[0])
-        q_pids, q_camids = _host_labels(q_pids, "q_pids", Q, who), _host_labels(q_camids, "q_camids", Q, who)
-        g_pids, g_camids = _host_labels(g_pids, "g_pids", G, who), _host_labels(g_camids, "g_camids", G, who)
+        q_pids, q_camids = host_labels(q_pids, "q_pids", Q, who), host_labels(q_camids, "q_camids", Q, who)
+        g_pids, g_camids = host_labels(g_pids, "g_pids", G, who), host_labels(g_camids, "g_camids", G, who)
     st = _gnn_sparse(X_q, X_g, k1, k2, precision, slab_rows)
     Q, G, dev = st["Q"], st["G"], st["col"].device
     acc = TopKAccumulator(Q, k, q_pids if given else None, q_camids if given else None, device=dev)
     if given:
-        g_pids, g_camids = _on(g_pids, dev), _on(g_camids, dev)
+        g_pids, g_camids = on_device(g_pids, dev), on_device(g_camids, dev)
     width = min(st["slab"], G)
     buf = torch.empty((Q, (width + 3) // 4 * 4), dtype=torch.float32, device=dev)
     for g0, g1, fill in _gnn_sparse_ranges(st, width):
         fill(buf, buf.shape[1])
-        acc._merge(buf, buf.shape[1], g1 - g0, g_pids[g0:g1] if given else None, g_camids[g0:g1] if given else None)
+        acc.merge(buf, buf.shape[1], g1 - g0, *((g_pids[g0:g1], g_camids[g0:g1]) if given else ()))
     return acc.result()
