@@ -147,6 +147,71 @@ __global__ void rownorm_kernel(const T* x, int64_t rows, int d, int metric, floa
   if (lane == 0) out[row] = metric == 0 ? s : 1.0f / fmaxf(sqrtf(s), 1e-12f);
 }
 
+// ---------------------------------------------------------------- single elements of the distance matrix
+// Sixteen elements of the fp32 distance matrix per wave, each with the bits distmat_kernel<float> gives it.  There an
+// element's inner product is one accumulator of v_mfma_f32_16x16x4_f32, fed k-tile after k-tile (32 columns, ascending)
+// with k = 4 kk + (lane >> 4) in step kk, the gallery side as the A operand and the query side as B (gemm_nt:
+// mfma16(fb, fa, acc)); the columns a k-tile pads are zeros and change nothing.  Here pair p of the wave is element
+// (p, p) of the 16 x 16 tile: lane (p, g = lane >> 4) supplies both rows of pair p at k = 4 kk + g, the same
+// instruction sequence runs over the d columns, and the lane that holds (p, p) -- column lane & 15, row
+// 4 (lane >> 4) + r -- hands it out.  The other 240 elements are not looked at.
+// col / row: this lane's pair's gallery-side and query-side descriptor rows.  Returns the pair's inner product on the
+// lanes with (lane >> 4) == (lane & 15) >> 2, anything elsewhere.
+__device__ __forceinline__ float pair_dot16(const float* __restrict__ row, const float* __restrict__ col, int d, int lane) {
+  const int g = lane >> 4;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  int k0 = 0;                                      // the same on every lane: the loops below never diverge
+  for (; k0 + 32 <= d; k0 += 32) {                 // one k-tile: eight loads a side in flight, then the eight steps
+    float a[8], b[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) { a[s] = col[k0 + 4 * s + g]; b[s] = row[k0 + 4 * s + g]; }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) acc = mfma16(a[s], b[s], acc);
+  }
+  for (; k0 < d; k0 += 4) acc = mfma16(col[k0 + g], row[k0 + g], acc);       // d % 4 == 0
+  const int r = lane & 3;
+  return r == 0 ? acc[0] : r == 1 ? acc[1] : r == 2 ? acc[2] : acc[3];
+}
+__device__ __forceinline__ bool pair_holder(int lane) { return (lane >> 4) == ((lane & 15) >> 2); }
+
+// out[p] = the element (idx1[p], idx2[p]) of the distance matrix of x1 (rows) and x2 (columns)
+__global__ __launch_bounds__(256) void distmat_pairs_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
+                                                            const float* __restrict__ n1, const float* __restrict__ n2,
+                                                            int d, int metric, const int32_t* __restrict__ idx1,
+                                                            const int32_t* __restrict__ idx2, int64_t pairs,
+                                                            float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t p = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (lane & 15);
+  const bool live = p < pairs;
+  const int64_t pc = live ? p : pairs - 1;         // idle lanes walk a real pair and drop the result
+  const int r = idx1[pc], c = idx2[pc];
+  const float v = pair_dot16(x1 + (int64_t)r * d, x2 + (int64_t)c * d, d, lane);
+  const DistEpi epi{nullptr, nullptr, nullptr, 0, 0, 0, metric, nullptr, nullptr, 0};
+  if (live && pair_holder(lane)) out[p] = epi.value(v, metric == 2 ? 0.f : n1[r], metric == 2 ? 0.f : n2[c]);
+}
+
+// The members of every owner row: out[i][p] = orig[e][i], e = members[i][p], p < counts[i], of the all-pairs matrix
+// orig = [[qq, qg], [qg^T, gg]] over x = [queries; gallery] (split = the first gallery row).  Each block has the row
+// operand the matrix path gives it: e, except that the Q x G block always has the query as its row operand, also where
+// it serves as orig[e in G][i in Q].  One workgroup per owner, its four waves take the member tiles in turn.
+__global__ __launch_bounds__(256) void distmat_member_pairs_kernel(const float* __restrict__ x, const float* __restrict__ nrm,
+                                                                   int d, int split, int metric,
+                                                                   const int32_t* __restrict__ counts,
+                                                                   const int32_t* __restrict__ members, int cap,
+                                                                   float* __restrict__ out) {
+  const int i = blockIdx.x, lane = threadIdx.x & 63;
+  const int n = min(counts[i], cap);
+  const DistEpi epi{nullptr, nullptr, nullptr, 0, 0, 0, metric, nullptr, nullptr, 0};
+  for (int p0 = (threadIdx.x >> 6) * 16; p0 < n; p0 += 64) {
+    const int p = p0 + (lane & 15);
+    const int e = members[(int64_t)i * cap + min(p, n - 1)];
+    const bool swap = e >= split && i < split;
+    const int r = swap ? i : e, c = swap ? e : i;
+    const float v = pair_dot16(x + (int64_t)r * d, x + (int64_t)c * d, d, lane);
+    if (p < n && pair_holder(lane)) out[(int64_t)i * cap + p] = epi.value(v, nrm[r], nrm[c]);
+  }
+}
+
 // ---------------------------------------------------------------- split-bf16 operands
 // An fp32 value is the exact sum of three bf16 pieces (8 + 8 + 8 mantissa bits): hi = bf16(x), mid = bf16(x - hi),
 // lo = bf16(x - hi - mid); every piece product is exact in the fp32 MFMA accumulator.  q.g is then a bf16 GEMM over
@@ -641,6 +706,44 @@ extern "C" int ieee_sqeuclid_distmat(const void* q, const void* g, int64_t m, in
     IEEE_REQUIRE(false, "distmat: unsupported dtype %d", dtype);
   }
   return launch_status("distmat");
+}
+
+extern "C" int ieee_distmat_pairs(const float* x1, const float* x2, int64_t m, int64_t n, int64_t d, const int32_t* idx1,
+                                  const int32_t* idx2, int64_t pairs, int metric, float* out, void* work, void* stream) {
+  IEEE_REQUIRE(x1 && x2 && work, "distmat_pairs: null pointer");
+  IEEE_REQUIRE(m > 0 && n > 0 && d > 0, "distmat_pairs: empty input (m=%ld n=%ld d=%ld)", (long)m, (long)n, (long)d);
+  IEEE_REQUIRE(d % 8 == 0, "distmat_pairs: feature dim %ld must be a multiple of 8", (long)d);
+  IEEE_REQUIRE(metric >= 0 && metric <= 2, "distmat_pairs: unknown metric %d", metric);
+  IEEE_REQUIRE(m < (1ll << 31) && n < (1ll << 31) && d < (1ll << 31), "distmat_pairs: too many rows or columns");
+  IEEE_REQUIRE(pairs >= 0 && pairs < (1ll << 36), "distmat_pairs: %ld pairs", (long)pairs);
+  if (pairs == 0) return IEEE_OK;
+  IEEE_REQUIRE(idx1 && idx2 && out, "distmat_pairs: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  float* n1 = (float*)work;
+  float* n2 = n1 + m;
+  if (metric != 2) {
+    rownorm_kernel<float><<<cdiv(m, 4), 256, 0, st>>>(x1, m, (int)d, metric, n1);
+    rownorm_kernel<float><<<cdiv(n, 4), 256, 0, st>>>(x2, n, (int)d, metric, n2);
+  }
+  distmat_pairs_kernel<<<(unsigned)cdiv(pairs, 64), 256, 0, st>>>(x1, x2, n1, n2, (int)d, metric, idx1, idx2, pairs, out);
+  return launch_status("distmat_pairs");
+}
+
+extern "C" int ieee_distmat_member_pairs(const float* x, int64_t rows, int64_t d, int64_t split, const int32_t* counts,
+                                         const int32_t* members, int64_t cap, int metric, float* out, void* work,
+                                         void* stream) {
+  IEEE_REQUIRE(x && counts && members && out && work, "distmat_member_pairs: null pointer");
+  IEEE_REQUIRE(rows > 0 && rows < (1ll << 31) && d > 0 && d < (1ll << 31) && d % 8 == 0,
+               "distmat_member_pairs: rows %ld, feature dim %ld (a multiple of 8)", (long)rows, (long)d);
+  IEEE_REQUIRE(split >= 0 && split <= rows && cap >= 1 && cap < (1ll << 31), "distmat_member_pairs: split %ld, cap %ld",
+               (long)split, (long)cap);
+  IEEE_REQUIRE(metric == 0 || metric == 1, "distmat_member_pairs: unknown metric %d", metric);
+  hipStream_t st = (hipStream_t)stream;
+  float* nrm = (float*)work;
+  rownorm_kernel<float><<<cdiv(rows, 4), 256, 0, st>>>(x, rows, (int)d, metric, nrm);
+  distmat_member_pairs_kernel<<<(unsigned)rows, 256, 0, st>>>(x, nrm, (int)d, (int)split, metric, counts, members, (int)cap,
+                                                              out);
+  return launch_status("distmat_member_pairs");
 }
 
 static int split_terms(int64_t scheme) {

@@ -49,6 +49,12 @@ def _check_rerank(rerank):
         raise ValueError("rerank must be False, True (k-reciprocal re-ranking) or 'gnn', got {!r}".format(rerank))
 
 
+def _check_rerank_from(rerank_from):
+    """where k-reciprocal re-ranking (rerank=True) takes its distances from: three finished matrices, or the descriptors"""
+    if rerank_from not in ('matrices', 'descriptors'):
+        raise ValueError("rerank_from must be 'matrices' or 'descriptors', got {!r}".format(rerank_from))
+
+
 def _check_stream_eval(stream_eval, rerank, use_metric_cuhk03):
     """stream_eval is the Market1501 protocol on one rank, on plain distances"""
     if not stream_eval:
@@ -142,7 +148,7 @@ class Engine(object):
             start_eval=0, eval_freq=-1, test_only=False, dist_metric='euclidean', normalize_feature=False,
             visrank=False, visrank_topk=10, use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False,
             rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None, stream_eval=False,
-            rerank_formulation=None):
+            rerank_formulation=None, rerank_from='matrices'):
         """engine.py:126-232.  As in the reference there is NO evaluation or checkpoint after the last epoch (the
         `(epoch + 1) != max_epoch` guard, :216), and re-ranking applies to test_only runs (its docstring, :171-172;
         the in-loop test call does not pass it on, :217-225).  rerank: False, True (k-reciprocal) or 'gnn' (see test;
@@ -153,11 +159,13 @@ class Engine(object):
             raise ValueError('vistsne can be set to True only if test_only=True')
         _check_rerank(rerank)
         _check_formulation(rerank_formulation)
+        _check_rerank_from(rerank_from)
         _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
         eval_args = dict(dist_metric=dist_metric, normalize_feature=normalize_feature, save_dir=save_dir,
                          use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, stream_eval=stream_eval)
         if test_only:
             self.test(rerank=rerank, rerank_k1=rerank_k1, rerank_k2=rerank_k2, rerank_formulation=rerank_formulation,
+                      rerank_from=rerank_from,
                       visrank=visrank, visrank_topk=visrank_topk, vistsne=vistsne, vistsne_labels=vistsne_labels, **eval_args)
             return
         began = time.time()
@@ -244,7 +252,7 @@ class Engine(object):
     # ---- evaluation ----------------------------------------------------------------------------------------------
     def test(self, dist_metric='euclidean', normalize_feature=False, visrank=False, visrank_topk=10, save_dir='',
              use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7, vistsne=False,
-             vistsne_labels=None, stream_eval=False, rerank_formulation=None):
+             vistsne_labels=None, stream_eval=False, rerank_formulation=None, rerank_from='matrices'):
         """every target dataset in turn (engine.py:287-337); returns the last one's mAP like the reference.
         rerank: False; True = k-reciprocal re-ranking (engine.py:402-406); 'gnn' = GNN re-ranking
         (ieee_amd.rerank.gnn_distmat with rerank_k1, rerank_k2 and formulation=rerank_formulation -- None, 'dense', 'sparse'
@@ -252,6 +260,9 @@ class Engine(object):
         always handed L2-normalised descriptors, F.normalize(., p=2, dim=1), whatever dist_metric and normalize_feature
         say: the method ranks by the raw inner product and the reference's driver feeds it normalised rows.  Any other
         string raises ValueError; other values keep their truthiness.
+        rerank_from (rerank=True alone; not in the reference): 'matrices' = the reference's way, three finished distance
+        matrices; 'descriptors' = ieee_amd.rerank.re_ranking_features, the same matrix bit for bit with no Q x Q and no
+        G x G matrix, for galleries whose matrices do not fit.  Another value is a ValueError.
         vistsne: after each report, the feature-space figure that the reference's evaluator draws under its visrank flag
         (engine.py:437-439, 463-490): t-SNE of the three 768-wide slices of the query descriptors into
         <save_dir>/vistsne_<name>/<labels>.jpg (ieee_amd.reidtools.show_points_multimodal).  vistsne_labels: the
@@ -261,6 +272,7 @@ class Engine(object):
         and report.  ValueError with rerank, with use_metric_cuhk03 or over more than one rank."""
         _check_rerank(rerank)
         _check_formulation(rerank_formulation)
+        _check_rerank_from(rerank_from)
         _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
         self.set_model_mode('eval')
         mAP = 0.0
@@ -274,7 +286,7 @@ class Engine(object):
                                         use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, rerank=rerank,
                                         rerank_k1=rerank_k1, rerank_k2=rerank_k2, vistsne=vistsne,
                                         vistsne_labels=vistsne_labels, stream_eval=stream_eval,
-                                        rerank_formulation=rerank_formulation)
+                                        rerank_formulation=rerank_formulation, rerank_from=rerank_from)
             if self.writer is not None:
                 self.writer.add_scalar('Test/{}/rank1'.format(name), rank1, self.epoch)
                 self.writer.add_scalar('Test/{}/mAP'.format(name), mAP, self.epoch)
@@ -332,11 +344,12 @@ class Engine(object):
     def _evaluate(self, dataset_name='', query_loader=None, gallery_loader=None, dist_metric='euclidean',
                   normalize_feature=False, visrank=False, visrank_topk=10, save_dir='', use_metric_cuhk03=False,
                   ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None,
-                  stream_eval=False, rerank_formulation=None):
+                  stream_eval=False, rerank_formulation=None, rerank_from='matrices'):
         """descriptors -> distance matrix -> CMC / mAP, printed like engine.py:339-441; returns (rank-1, mAP).
         stream_eval: no distance matrix, the gallery goes by in slabs (see test)"""
         _check_rerank(rerank)
         _check_formulation(rerank_formulation)
+        _check_rerank_from(rerank_from)
         _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
         if visrank and ddp.world_size() > 1:
             raise RuntimeError('visrank needs the whole distance matrix, which a sharded evaluation over {} ranks never '
@@ -373,8 +386,14 @@ class Engine(object):
             say('Computing CMC and mAP for {} (queries sharded over {} ranks)'.format(dataset_name, ddp.world_size()))
             cmc, mAP = ddp.sharded_evaluate_rank(qf, gf, q_pids, g_pids, q_camids, g_camids, metric=dist_metric)
         else:
-            distmat = compute_distance_matrix(qf, gf, dist_metric)
-            if rerank == 'gnn':     # GPU-Re-Ranking/gnn_reranking.py on normalised descriptors, as its driver feeds it
+            from_descriptors = bool(rerank) and rerank != 'gnn' and rerank_from == 'descriptors'
+            if not from_descriptors:
+                distmat = compute_distance_matrix(qf, gf, dist_metric)
+            if from_descriptors:    # the same re-ranked matrix, bit for bit, with no Q x Q and no G x G matrix
+                say('Applying person re-ranking ...')
+                from .rerank import re_ranking_features
+                distmat = re_ranking_features(qf, gf, metric=dist_metric)
+            elif rerank == 'gnn':    # GPU-Re-Ranking/gnn_reranking.py on normalised descriptors, as its driver feeds it
                 say('Applying person re-ranking ... (gnn)')
                 from .rerank import gnn_distmat
                 distmat = gnn_distmat(F.normalize(qf, p=2, dim=1), F.normalize(gf, p=2, dim=1), rerank_k1, rerank_k2,

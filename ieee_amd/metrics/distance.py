@@ -98,6 +98,42 @@ def compute_distance_matrix(input1, input2, metric='euclidean', precision=None):
     return distmat
 
 
+def _pair_index(idx, rows, name):
+    """-> int64 host or device tensor, 1-D, every entry in [0, rows): checked where the indices are"""
+    idx = torch.as_tensor(idx)
+    if idx.dim() != 1 or idx.dtype.is_floating_point or idx.dtype == torch.bool:
+        raise ValueError("pair_distances: {} must be a 1-D integer array, got {} {}".format(name, idx.dtype, tuple(idx.shape)))
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= rows):
+        raise ValueError("pair_distances: {} has entries outside [0, {})".format(name, rows))
+    return idx
+
+
+def pair_distances(input1, input2, idx1, idx2, metric='euclidean'):
+    """compute_distance_matrix(input1, input2, metric)[idx1, idx2] in fp32 without the matrix: a 1-D fp32 tensor on
+    input1's device, entry p the distance of input1[idx1[p]] and input2[idx2[p]] with the bits the matrix has there
+    (ieee_distmat_pairs: the pairs go through the matrix GEMM's own MFMA sequence, norms and epilogue).  idx1, idx2:
+    1-D integer tensors or arrays of one length, on the host or the device."""
+    from ._stream import check_metric
+    metric_id = check_metric(metric)
+    assert isinstance(input1, torch.Tensor) and isinstance(input2, torch.Tensor)
+    if input1.dim() != 2 or input2.dim() != 2 or input1.size(1) != input2.size(1) or not input1.size(0) or not input2.size(0):
+        raise ValueError("pair_distances: expected input1 [m, d] and input2 [n, d] with m, n >= 1, got {} and {}".format(
+            tuple(input1.shape), tuple(input2.shape)))
+    idx1, idx2 = _pair_index(idx1, input1.size(0), "idx1"), _pair_index(idx2, input2.size(0), "idx2")
+    if idx1.numel() != idx2.numel():
+        raise ValueError("pair_distances: {} row indices for {} column indices".format(idx1.numel(), idx2.numel()))
+    lib = _lib.require_gpu()
+    a, dev = _as_device(input1, torch.float32)
+    b, _ = _as_device(input2, torch.float32)
+    a, b = _pad8(a), _pad8(b)
+    i1, i2 = idx1.to(a.device, torch.int32).contiguous(), idx2.to(a.device, torch.int32).contiguous()
+    out = torch.empty(i1.numel(), dtype=torch.float32, device=a.device)
+    work = torch.empty((a.shape[0] + b.shape[0]) * 4, dtype=torch.uint8, device=a.device)
+    _lib.check(lib.ieee_distmat_pairs(_lib.ptr(a), _lib.ptr(b), a.shape[0], b.shape[0], a.shape[1], _lib.ptr(i1),
+                                      _lib.ptr(i2), i1.numel(), metric_id, _lib.ptr(out), _lib.ptr(work), _lib.stream()))
+    return out if dev.type == "cuda" else out.to(dev)
+
+
 def euclidean_squared_distance(input1, input2, precision=None):
     """distance.py:49-64 — |a|^2 + |b|^2 - 2 a.b (squared, no sqrt)."""
     return _distmat(input1, input2, 0, precision=precision)

@@ -8,8 +8,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .metrics._stream import (SlabDistances, check_k, check_labels_all_or_none, check_slab, device_matrix, host_labels,
-                              on_device)
+from .metrics import _stream
+from .metrics import distance as _dist
+from .metrics._stream import (SlabDistances, check_k, check_labels_all_or_none, check_metric, check_slab, device_matrix,
+                              host_labels, on_device)
 from .metrics.search import TopKAccumulator
 
 
@@ -73,6 +75,182 @@ def re_ranking(q_g_dist, q_q_dist, g_g_dist, k1=20, k2=6, lambda_value=0.3, form
     if isinstance(q_g_dist, torch.Tensor) and q_g_dist.is_cuda:
         return out
     return out.cpu().numpy()
+
+
+# ---- k-reciprocal re-ranking from descriptors (ieee_amd/csrc/rerank_stream.hip): no Q x Q, G x G or (Q+G)^2 tensor ------
+RERANK_MAX_K = 64        # rerank_sparse.h: k1 + 1 <= RS_MAXK
+
+
+def stream_slab_rows(slab_rows, who="re_ranking_features"):
+    """-> the rows on either side of one distance GEMM: slab_rows checked, or for None the largest multiple of 128
+    whose square fp32 buffer stays within SLAB_BUDGET_BYTES"""
+    if slab_rows is None:
+        return int((_stream.SLAB_BUDGET_BYTES // 4) ** 0.5) // 128 * 128
+    return check_slab(slab_rows, 0, who, "slab_rows")
+
+
+def stream_pieces(n, slab_rows, cut=None):
+    """[0, n) in pieces of at most slab_rows, none across `cut` (the first gallery row of [queries; gallery]): a list
+    of (lo, hi)"""
+    cuts = [0, n] if cut is None or not 0 < cut < n else [0, cut, n]
+    return [(lo, min(lo + slab_rows, hi)) for b, hi in zip(cuts[:-1], cuts[1:]) for lo in range(b, hi, slab_rows)]
+
+
+def stream_schedule(n, slab_rows, cut=None):
+    """The blocks (a0, a1, i0, i1) of the n x n all-pairs matrix in the order the strip passes visit them: for every
+    strip of owner columns [i0, i1), every slab of rows [a0, a1).  Every (row, column) pair lies in exactly one block,
+    no block is longer than slab_rows on either side, and none crosses `cut`, so one block is one distance GEMM whose
+    operands are those of the matrix path."""
+    pieces = stream_pieces(n, slab_rows, cut)
+    return [(a0, a1, i0, i1) for i0, i1 in pieces for a0, a1 in pieces]
+
+
+def _stream_checks(X_q, X_g, k1, k2, metric, slab_rows, precision, who):
+    """every argument check, on the host, before the library or a device is needed -> (metric_id, Q, G, k1, k2, slab)"""
+    metric_id = check_metric(metric)
+    if precision is None:
+        precision = os.environ.get("IEEE_DISTMAT_PRECISION", "fp32")
+    if precision != "fp32":
+        raise ValueError("%s: precision must be None or 'fp32' (the bits of the fp32 matrix path are the contract), got %r"
+                         % (who, precision))
+    sq, sg = tuple(np.shape(X_q)), tuple(np.shape(X_g))
+    if len(sq) != 2 or len(sg) != 2 or sq[1] != sg[1]:
+        raise ValueError("%s: expected X_q [Q, d] and X_g [G, d], got %s and %s" % (who, sq, sg))
+    Q, G = int(sq[0]), int(sg[0])
+    for name, v in (("k1", k1), ("k2", k2)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("%s: %s must be an integer, got %r" % (who, name, v))
+    k1, k2 = int(k1), int(k2)
+    if Q < 1 or G < 1:
+        raise ValueError("%s: empty query or gallery set (Q = %d, G = %d)" % (who, Q, G))
+    if not (1 <= k1 and k1 + 1 <= RERANK_MAX_K and k1 + 1 <= Q + G < 2 ** 31):
+        raise ValueError("%s: k1 = %d out of range (1 .. %d, and k1 + 1 <= Q + G = %d < 2^31)"
+                         % (who, k1, RERANK_MAX_K - 1, Q + G))
+    if not 1 <= k2 <= k1 + 1:
+        raise ValueError("%s: k2 = %d out of range (1 .. k1 + 1 = %d)" % (who, k2, k1 + 1))
+    return metric_id, Q, G, k1, k2, stream_slab_rows(slab_rows, who)
+
+
+def stream_layout(Q, G, k1, k2, slab_rows=None):
+    """where the ieee_rerank_stream_* calls keep their intermediates in the workspace (include/ieee_amd.h): sparse_layout's
+    fields, then keys (the running lists), strip and range (the longest strip of columns and gallery range)"""
+    import ctypes
+    fields = (ctypes.c_int64 * 14)()
+    _lib.check(_lib.load().ieee_rerank_stream_layout(Q, G, int(k1), int(k2), stream_slab_rows(slab_rows),
+                                                     ctypes.cast(fields, ctypes.c_void_p)))
+    names = ("K", "capV", "capVq", "rank", "V_n", "V_idx", "V_val", "Vq_n", "Vq_idx", "Vq_val", "colmax", "keys", "strip",
+             "range")
+    return dict(zip(names, (int(f) for f in fields)))
+
+
+def _rerank_stream(X_q, X_g, k1, k2, metric, slab_rows, precision, who):
+    """steps A - D -> dict(lib, Q, G, slab, x [Q + G, d] (fp32, d padded to 8), metric_id, args (what every
+    ieee_rerank_stream_* call ends with), work).  Two sweeps of distance GEMMs over the blocks of stream_schedule, each
+    into one reused buffer of at most slab x slab distances, then one gathered-operand GEMM for the members' distances."""
+    metric_id, Q, G, k1, k2, slab = _stream_checks(X_q, X_g, k1, k2, metric, slab_rows, precision, who)
+    lib = _lib.require_gpu()
+    q, g = _dev(X_q), _dev(X_g)
+    N, dev = Q + G, q.device
+    x = _gnn_features(q, g, (q.shape[1] + 7) // 8 * 8)
+    del q, g
+    nbytes = int(lib.ieee_rerank_stream_workspace_bytes(Q, G, k1, k2, slab))
+    if nbytes < 0:
+        _lib.check(-1)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    args = (Q, G, k1, k2, slab, _lib.ptr(work), nbytes)
+    _lib.check(lib.ieee_rerank_stream_begin(*args, _lib.stream()))
+    pieces = stream_pieces(N, slab, Q)
+    longest = max(hi - lo for lo, hi in pieces)
+    buf = torch.empty(longest * ((longest + 3) // 4 * 4), dtype=torch.float32, device=dev)
+    norms = torch.empty(2 * longest * 4, dtype=torch.uint8, device=dev)
+
+    def block(step, a0, a1, i0, i1):
+        # the Q x G block has the query as its row operand wherever it is used (cosine's epilogue is not symmetric):
+        # as orig[a in G][i in Q] it is produced [i][a] and read transposed
+        transposed = a0 >= Q and i1 <= Q
+        rows, cols = ((i0, i1), (a0, a1)) if transposed else ((a0, a1), (i0, i1))
+        ld = (cols[1] - cols[0] + 3) // 4 * 4
+        _dist._launch(lib, x[rows[0]:rows[1]], x[cols[0]:cols[1]], metric_id, torch.float32, "fp32", buf, ld, norms)
+        sa, si = (1, ld) if transposed else (ld, 1)
+        _lib.check(lib.ieee_rerank_stream_block(step, _lib.ptr(buf), sa, si, a0, a1, i0, i1, *args, _lib.stream()))
+
+    schedule = stream_schedule(N, slab, Q)
+    for s in range(0, len(schedule), len(pieces)):      # one strip: A over all its slabs, then B -- a strip's maxima are
+        for step in (0, 1):                             # complete before its keys are formed
+            for blk in schedule[s:s + len(pieces)]:
+                block(step, *blk)
+    del buf
+    _lib.check(lib.ieee_rerank_stream_sets(*args, _lib.stream()))
+    # C2: the members' distances, each with the matrix's bits, from the gathered-operand GEMM -- no third sweep
+    L = stream_layout(Q, G, k1, k2, slab)
+    norms = torch.empty(N * 4, dtype=torch.uint8, device=dev)
+    _lib.check(lib.ieee_distmat_member_pairs(_lib.ptr(x), N, x.shape[1], Q, _lib.ptr(work[L["V_n"]:]),
+                                             _lib.ptr(work[L["V_idx"]:]), L["capV"], metric_id,
+                                             _lib.ptr(work[L["V_val"]:]), _lib.ptr(norms), _lib.stream()))
+    _lib.check(lib.ieee_rerank_stream_rows(*args, _lib.stream()))
+    del norms
+    return dict(lib=lib, Q=Q, G=G, slab=slab, x=x, metric_id=metric_id, args=args, work=work)
+
+
+def _rerank_stream_ranges(st, lambda_value):
+    """steps E and F, gallery range by gallery range: yields (g0, g1, fill), fill(out, ldo) writing the range's
+    re-ranked distances into out (a tensor whose first element is column g0 of row 0, row stride ldo)"""
+    lib, Q, G, x = st["lib"], st["Q"], st["G"], st["x"]
+    distances = SlabDistances(lib, x[:Q], st["metric_id"], torch.float32, "fp32", x.device)
+    width = min(st["slab"], G)
+    for g0 in range(0, G, width):
+        g1 = min(g0 + width, G)
+
+        def fill(out, ldo, g0=g0, g1=g1):
+            d, ldd, _ = distances.stage(x[Q + g0:Q + g1])
+            _lib.check(lib.ieee_rerank_stream_range(_lib.ptr(d), ldd, g0, g1, float(lambda_value), _lib.ptr(out), ldo,
+                                                    *st["args"], _lib.stream()))
+        yield g0, g1, fill
+
+
+def re_ranking_features(X_q, X_g, k1=20, k2=6, lambda_value=0.3, metric='euclidean', slab_rows=None, precision=None):
+    """k-reciprocal re-ranking from the descriptors X_q [Q, d] and X_g [G, d] (tensors on the host or the device, or
+    numpy arrays; converted to fp32): the [Q, G] fp32 matrix, on the device, that re_ranking(cd(X_q, X_g), cd(X_q, X_q),
+    cd(X_g, X_g), k1, k2, lambda_value, formulation='sparse') returns for cd = compute_distance_matrix(., ., metric) in
+    fp32, bit for bit -- with no [Q, Q], [G, G] or [Q+G, Q+G] tensor.  The distances are produced block by block by the
+    distance GEMM, at most slab_rows rows on either side of one GEMM (None: one buffer within SLAB_BUDGET_BYTES), in
+    two sweeps over the (Q+G)^2 pairs (column maxima, then the k1+1 nearest of every row), and the distances to the
+    members of the k-reciprocal sets by a gathered-operand GEMM (ieee_distmat_member_pairs); the result has the same
+    bits for every slab_rows.  Device memory: the
+    descriptors, the sparse workspace, one distance buffer and the output.  precision: None or 'fp32' only."""
+    st = _rerank_stream(X_q, X_g, k1, k2, metric, slab_rows, precision, "re_ranking_features")
+    Q, G = st["Q"], st["G"]
+    out = torch.empty((Q, G), dtype=torch.float32, device=st["x"].device)
+    for g0, g1, fill in _rerank_stream_ranges(st, lambda_value):
+        fill(out[:, g0:], G)
+    return out
+
+
+def rerank_search_topk(X_q, X_g, k, k1=20, k2=6, lambda_value=0.3, metric='euclidean', q_pids=None, g_pids=None,
+                       q_camids=None, g_camids=None, slab_rows=None, precision=None):
+    """The k nearest kept gallery entries of every query under k-reciprocal re-ranking, without the [Q, G] matrix:
+    -> (indices int64 [Q, k], distances fp32 [Q, k]) on the device, what rank_topk(re_ranking_features(X_q, X_g, ...), k,
+    ...) lists, bit for bit.  Each gallery range's finished rows go from one reused [Q, slab_rows] buffer through
+    ieee_rank_topk_merge into the running lists.  Labels as in search_topk: all four or none."""
+    who = "rerank_search_topk"
+    k = check_k(k, who)
+    given = check_labels_all_or_none(q_pids, g_pids, q_camids, g_camids, who)
+    _stream_checks(X_q, X_g, k1, k2, metric, slab_rows, precision, who)
+    if given:
+        Q, G = int(np.shape(X_q)[0]), int(np.shape(X_g)[0])
+        q_pids, q_camids = host_labels(q_pids, "q_pids", Q, who), host_labels(q_camids, "q_camids", Q, who)
+        g_pids, g_camids = host_labels(g_pids, "g_pids", G, who), host_labels(g_camids, "g_camids", G, who)
+    st = _rerank_stream(X_q, X_g, k1, k2, metric, slab_rows, precision, who)
+    Q, G, dev = st["Q"], st["G"], st["x"].device
+    acc = TopKAccumulator(Q, k, q_pids if given else None, q_camids if given else None, device=dev)
+    if given:
+        g_pids, g_camids = on_device(g_pids, dev), on_device(g_camids, dev)
+    width = min(st["slab"], G)
+    buf = torch.empty((Q, (width + 3) // 4 * 4), dtype=torch.float32, device=dev)
+    for g0, g1, fill in _rerank_stream_ranges(st, lambda_value):
+        fill(buf, buf.shape[1])
+        acc.merge(buf, buf.shape[1], g1 - g0, *((g_pids[g0:g1], g_camids[g0:g1]) if given else ()))
+    return acc.result()
 
 
 # ---- GNN re-ranking (the reference's torchreid/utils/GPU-Re-Ranking/gnn_reranking.py) ----------------------------------

@@ -55,6 +55,20 @@ int ieee_device_is_gfx950(void);
  * (out = -q_i.g_j, no norms: what ieee_gnn_rerank ranks). */
 int ieee_sqeuclid_distmat(const void* q, const void* g, int64_t m, int64_t n, int64_t d, int dtype,
                           int metric, float* out, int64_t ldo, void* work, void* stream);
+/* Single elements of that matrix (dtype IEEE_F32), each with the bits ieee_sqeuclid_distmat gives it: out[p] = the
+ * element (idx1[p], idx2[p]) of the matrix of x1 [m][d] (rows) and x2 [n][d] (columns), p < pairs.  A gathered-operand
+ * GEMM: sixteen pairs per wave go through the same v_mfma_f32_16x16x4_f32 sequence as the matrix's tiles (the same k
+ * to the same lane group, ascending, one accumulator per element), with the same row norms and the same epilogue.
+ * idx1, idx2: int32 on the device, every index inside its operand (not checked: they are device data).  work: >=
+ * (m+n)*4 bytes.
+ * ieee_distmat_member_pairs: the same for the members of owner rows of the all-pairs matrix orig = [[qq, qg], [qg^T,
+ * gg]] over x = [queries; gallery] [rows][d], split = the number of queries: out[i][p] = orig[e][i], e = members[i][p],
+ * p < counts[i] (members, out: [rows][cap]).  Every element has the row operand the matrix path gives it: e, but the
+ * query where e is a gallery row and i a query.  metric 0 or 1.  work: >= rows*4 bytes. */
+int ieee_distmat_pairs(const float* x1, const float* x2, int64_t m, int64_t n, int64_t d, const int32_t* idx1,
+                       const int32_t* idx2, int64_t pairs, int metric, float* out, void* work, void* stream);
+int ieee_distmat_member_pairs(const float* x, int64_t rows, int64_t d, int64_t split, const int32_t* counts,
+                              const int32_t* members, int64_t cap, int metric, float* out, void* work, void* stream);
 /* the same matrix from fp32 rows on the 16-bit matrix cores: every value is split into 16-bit pieces that sum to it
  * and q.g becomes ONE 16-bit GEMM over the piece products, smallest first, accumulated in fp32 (each product is exact
  * there).  scheme:
@@ -694,6 +708,40 @@ int ieee_rerank_sparse(const float* q_g_dist, const float* q_q_dist, const float
  * [N][capV] fp32, Vq counts, Vq columns [N][capVq], Vq values, column maxima [N] (bits of fp32)}.  Vq is absent
  * (capVq = 0) when k2 = 1.  Row r of V holds counts[r] entries in ascending column order. */
 int ieee_rerank_sparse_layout(int64_t Q, int64_t G, int64_t k1, int64_t k2, int64_t* fields);
+/* The same re-ranking from descriptors (ieee_amd/csrc/rerank_stream.hip): ieee_rerank_sparse's steps and output bits
+ * with no Q x Q, G x G or (Q+G)^2 input.  The virtual matrix orig = [[qq, qg], [qg^T, gg]] (N = Q+G rows and columns)
+ * reaches the library block by block: the caller runs ieee_sqeuclid_distmat on the descriptors of a slab of rows
+ * [a0, a1) and a strip of columns [i0, i1), each on one side of Q and at most `slab` long, into a buffer of its own and
+ * hands that to ieee_rerank_stream_block.  Element (a, i) is buf[(a - a0) * sa + (i - i0) * si]: (sa, si) = (ld, 1), or
+ * (1, ld) where the Q x G block -- always produced with the query as the row operand, as the matrix path produces it --
+ * serves as orig[a in G][i in Q].  The order of calls, all on one stream, every one with the same Q, G, k1, k2, slab:
+ *   ieee_rerank_stream_begin;
+ *   for every strip: pass 0 over all its slabs (column maxima), then pass 1 over all its slabs (the k1+1 nearest of
+ *     every column, as running lists that any number of slabs merge into; needs the strip's maxima complete);
+ *   ieee_rerank_stream_sets (the ranking from the lists; the members of every row's expanded k-reciprocal set, counts
+ *     and ascending members where ieee_rerank_stream_layout says V's are);
+ *   ieee_distmat_member_pairs on those counts and members, writing into V's values (the members' distances);
+ *   ieee_rerank_stream_rows (the weights V from those distances, and their query expansion Vq);
+ *   ieee_rerank_stream_range for gallery ranges [g0, g1), g1 - g0 <= slab, in any order: dist holds the range's Q x
+ *     (g1 - g0) distances (row stride ldd), and row i of the re-ranked distances goes to out + i * ldo.
+ * Bounds as ieee_rerank_sparse, and slab >= 1.  The workspace is that of ieee_rerank_sparse with the inverted index
+ * sized for one range: a data-independent bound, -1 for arguments out of range.  ieee_rerank_stream_layout: fields[14] =
+ * the 11 of ieee_rerank_sparse_layout, then the byte offset of the running lists [N][k1+1] uint64 (bits(D) << 32 | j,
+ * valid between pass 1 and ieee_rerank_stream_sets), the longest strip and the longest gallery range. */
+int64_t ieee_rerank_stream_workspace_bytes(int64_t Q, int64_t G, int64_t k1, int64_t k2, int64_t slab);
+int ieee_rerank_stream_layout(int64_t Q, int64_t G, int64_t k1, int64_t k2, int64_t slab, int64_t* fields);
+int ieee_rerank_stream_begin(int64_t Q, int64_t G, int64_t k1, int64_t k2, int64_t slab, void* work, int64_t work_bytes,
+                             void* stream);
+int ieee_rerank_stream_block(int64_t pass, const float* buf, int64_t sa, int64_t si, int64_t a0, int64_t a1, int64_t i0,
+                             int64_t i1, int64_t Q, int64_t G, int64_t k1, int64_t k2, int64_t slab, void* work,
+                             int64_t work_bytes, void* stream);
+int ieee_rerank_stream_sets(int64_t Q, int64_t G, int64_t k1, int64_t k2, int64_t slab, void* work, int64_t work_bytes,
+                            void* stream);
+int ieee_rerank_stream_rows(int64_t Q, int64_t G, int64_t k1, int64_t k2, int64_t slab, void* work, int64_t work_bytes,
+                            void* stream);
+int ieee_rerank_stream_range(const float* dist, int64_t ldd, int64_t g0, int64_t g1, double lambda_value, float* out,
+                             int64_t ldo, int64_t Q, int64_t G, int64_t k1, int64_t k2, int64_t slab, void* work,
+                             int64_t work_bytes, void* stream);
 /* GNN re-ranking, torchreid/utils/GPU-Re-Ranking/gnn_reranking.py:27-59 with its build_adjacency_matrix and
  * gnn_propagate kernels: device features xq [Q][d], xg [G][d] fp32 (d % 8 == 0, nothing is normalised here) ->
  * out [Q][G] fp32 = 1 - sim, sim the cosine of the rows that two rounds of propagation leave, so that ascending out is
