@@ -693,7 +693,7 @@ __global__ __launch_bounds__(256, (BN == 256 ? 2 : (PIPE == 1 ? 4 : (PIPE == 5 ?
       LoaderIm2colNT<T, 4, true> la;
       la.init(src, a.g, m0, ch);
       gemm_nt_dma<128, BN, PIPE>(la, lbd, epi, a.ktiles, m0, n0, smem);
-    } else if (a.g.R == 1 && a.g.S == 1 && a.g.mul == 1 && a.g.off == 0 && a.g.div == 1) {
+    } else if (a.g.R == 1 && a.g.S == 1 && a.g.mul == 1 && a.g.off == 0 && a.g.div == 1) {   // (gather_plain_1x1 restates this)
       // 1x1 / stride 1 / no padding (two thirds of the launches): im2col(X) is X itself, a plain [pixels][C] matrix --
       // no pixel decode, no tap masks (their set-up rivals the whole k-loop of the K = 64..256 layers), and the same
       // lean issue as the weights (C is a multiple of 64 on this path: no k tail)
@@ -1050,11 +1050,11 @@ __global__ __launch_bounds__(256, 4) void stem_conv_kernel(const bf16* __restric
 }
 
 // the shapes the direct stem covers: 8x8 / stride 2 / no padding over 4 channels, 64 output channels, 64 output columns
-static bool stem_eligible(const GatherGeom& g, int N, int ldw, int mode, const void* addend) {
+static bool stem_eligible(const GatherGeom& g, int N, int ldw, int mode, bool has_addend) {
   static const bool on = !(getenv("IEEE_STEM_DIRECT") && atoi(getenv("IEEE_STEM_DIRECT")) == 0);
   return on && g.R == 8 && g.S == 8 && g.Cs == 4 && g.mul == 2 && g.off == 0 && g.sgn == 1 && g.div == 1 && !g.perm && N == 64 &&
          g.Wo == 64 && (g.Ho & 1) == 0 && g.Ws == 2 * 64 + 6 && g.Hs == 2 * g.Ho + 6 && ldw == 256 && (mode == 0 || mode == 1 || mode == 3) &&
-         addend == nullptr;
+         !has_addend;
 }
 
 
@@ -1819,20 +1819,34 @@ static void launch_gather_inst(dim3 grid, size_t smem, hipStream_t st, const T* 
   launch_timed(conv_gather_kernel<T, BN, SLOW, MODE, PIPE, VAR>, grid, smem, st, src, w, dst, addend, bn_partial, a, bs);
 }
 
+// im2col(X) is X itself: the run-time test by which conv_gather_kernel's LDS-DMA path picks its plain-matrix loader, restated
+// for gather_form (the kernel keeps its own expression: calling a shared function there changed its register allocation)
+static bool gather_plain_1x1(const GatherGeom& g) { return g.R == 1 && g.S == 1 && g.mul == 1 && g.off == 0 && g.div == 1; }
+
+// the epilogue variant (StagedStoreEpi VAR) of a gather launch: own instantiations of the single-stage bf16 pipeline only
+static int gather_var(bool is_bf16, int bn, int pipe, int mode, bool perm, bool addend_s2, bool y2) {
+  if (!(pipe == 1 && bn != 256 && is_bf16)) return 0;
+  if (perm && (mode == 0 || mode == 2)) return 1;   // stride-2 dgrad in parity-class row order
+  if (addend_s2 && mode == 2) return 2;             // compact stride-2 addend
+  if (y2 && mode == 2) return 3;                    // + the sums of a second BatchNorm
+  return 0;
+}
+
 template <typename T, int BN, int PIPE>
 static void launch_gather_mode(int mode, dim3 grid, size_t smem, hipStream_t st, const T* src, const T* w, T* dst,
                                const T* addend, float* bn_partial, const ConvArgs& a, const BwdStats& bs) {
-  if constexpr (PIPE == 1 && BN != 256 && sizeof(T) == 2) {   // stride-2 dgrad in parity-class row order: its own instantiations
-    if (a.g.perm && (mode == 0 || mode == 2)) {
+  if constexpr (PIPE == 1 && BN != 256 && sizeof(T) == 2) {
+    const int var = gather_var(true, BN, PIPE, mode, a.g.perm != 0, bs.addend_s2 != 0, bs.y2 != nullptr);
+    if (var == 1) {
       if (mode == 2) launch_gather_inst<T, BN, false, 2, PIPE, 1>(grid, smem, st, src, w, dst, addend, bn_partial, a, bs);
       else launch_gather_inst<T, BN, false, 0, PIPE, 1>(grid, smem, st, src, w, dst, addend, nullptr, a, bs);
       return;
     }
-    if (bs.addend_s2 && mode == 2) {   // compact stride-2 addend (see StagedStoreEpi VAR 2)
+    if (var == 2) {
       launch_gather_inst<T, BN, false, 2, PIPE, 2>(grid, smem, st, src, w, dst, addend, bn_partial, a, bs);
       return;
     }
-    if (bs.y2 != nullptr && mode == 2) {   // + the sums of a second BatchNorm (StagedStoreEpi VAR 3)
+    if (var == 3) {
       launch_gather_inst<T, BN, false, 2, PIPE, 3>(grid, smem, st, src, w, dst, addend, bn_partial, a, bs);
       return;
     }
@@ -1868,6 +1882,76 @@ static GatherPlan plan_gather(int M, int N, int ktiles, int groups) {
   return p;
 }
 
+// The form of ONE forward / dgrad launch: every choice the launcher makes from the shape and the options of the call, made
+// here (host arithmetic only) so that launch_gather and the plan query (ieee_conv_plan) cannot disagree.
+struct GatherForm {
+  int family = 0;              // 0 conv_gather_kernel, 1 conv3x3_patch_kernel, 2 stem_conv_kernel
+  int bn = 128, pipe = 0;      // template arguments BN, PIPE
+  int pipe_lds = 0;            // the pipeline the dynamic LDS of a gather launch is sized for (the plan's, before the y2 form forces 1)
+  int mode = 0, var = 0, slow = 0, wlog = 0, style = 0;
+  int loader = 1;              // 0 plain 1x1 matrix, 1 im2col, 2 im2col over parity-class rows (chosen inside the kernel)
+  int perm = 0;                // GatherGeom::perm as the kernel sees it
+  int tiles_m = 0, tiles_n = 0;
+  const char* refuse = nullptr;   // non-null: the launcher returns IEEE_ERR_UNSUPPORTED with this text
+};
+static GatherForm gather_form(bool is_bf16, GatherGeom g, int M, int N, int Ktrue, int ldw, int groups, bool slow, bool stats,
+                              bool bwd, bool affine, bool has_addend, bool addend_s2, bool y2) {
+  GatherForm f;
+  const int ktiles = cdiv(Ktrue, is_bf16 ? ImgNT<bf16>::BK : ImgNT<float>::BK);
+  GatherPlan plan{N <= 64 ? 64 : 128, 0};
+  if (is_bf16 && !slow) plan = plan_gather(M, N, ktiles, groups);
+  if (plan.pipe != 1 || plan.bn == 256 || affine || (stats && !bwd)) g.perm = 0;   // class-major rows: default pipeline, dgrad modes
+  f.perm = g.perm;
+  f.slow = slow ? 1 : 0;
+  f.tiles_m = cdiv(M, 128);
+  f.tiles_n = cdiv(N, plan.bn);
+  f.bn = plan.bn;
+  f.pipe = f.pipe_lds = plan.pipe;
+  if (stats && (slow || !is_bf16)) { f.refuse = "conv: fused BN statistics need the bf16 vector path"; return f; }
+  if (affine && slow) { f.refuse = "conv: the fused inference BatchNorm needs the vector path"; return f; }
+  f.mode = affine ? 3 : ((stats && bwd) ? 2 : (stats ? 1 : 0));
+  if (y2) {
+    // the second BatchNorm's sums exist as ONE instantiation (plain-row dgrad epilogue of the single-stage bf16 pipeline):
+    // force that pipeline, refuse the forms that have their own epilogue variants
+    if (!(is_bf16 && !slow && f.mode == 2 && !g.perm && !addend_s2 && plan.bn != 256 && !patch_eligible(g, M))) {
+      f.refuse = "conv: the sums of a second BatchNorm need a plain bf16 dgrad (no stride-2 row order, no "
+                 "compact addend, no 3x3 patch form)";
+      return f;
+    }
+    f.pipe = 1;
+  }
+  if (is_bf16 && !slow) {
+    if (stem_eligible(g, N, ldw, f.mode, has_addend)) {
+      f.family = 2; f.bn = 64; f.pipe = 0; f.tiles_n = 1;
+      return f;
+    }
+    if (plan.bn != 256 && !addend_s2 && patch_eligible(g, M)) {
+      static const int f_style_env = getenv("IEEE_PATCH_STYLE") ? atoi(getenv("IEEE_PATCH_STYLE")) : -1;
+      static const int f_bn = getenv("IEEE_PATCH_BN") ? atoi(getenv("IEEE_PATCH_BN")) : 0;
+      const int bn = (N <= 64) ? 64 : (f_bn ? f_bn : plan.bn);
+      // measured per layer (scripts/experiments/scan_r3g.sh): the two-stage weight ring wins where the tile is 128 x 64 (39 KB of LDS keeps
+      // 4 workgroups per CU: 256->256 755 -> 923 TFLOP/s, 64->64 608 -> 650) and loses at 128 x 128 (55 KB -> 2 per CU:
+      // 512->512 1 320 -> 1 234, 128->128 871 -> 767)
+      f.style = (f_style_env >= 0 ? f_style_env : (bn == 64 ? 0 : 1)) == 0 ? 0 : 1;
+      f.family = 1;
+      f.bn = bn == 64 ? 64 : 128;
+      f.pipe = 0;
+      f.tiles_n = cdiv(N, bn);
+      f.wlog = g.Ws == 8 ? 3 : (g.Ws == 16 ? 4 : 5);
+      return f;
+    }
+  }
+  if (slow || !is_bf16) {      // register staging; the element-gather kernel has the plain store epilogue only
+    f.bn = plan.bn == 64 ? 64 : 128;
+    f.pipe = 0;
+    if (slow) f.mode = 0;
+    return f;
+  }
+  f.var = gather_var(true, f.bn, f.pipe, f.mode, g.perm != 0, addend_s2, y2);
+  if (f.pipe > 0) f.loader = f.var == 1 ? 2 : (gather_plain_1x1(g) ? 0 : 1);
+  return f;
+}
+
 template <typename T>
 static int launch_gather(const T* src, const T* w, T* dst, const T* addend, const GatherGeom& g, int M, int N,
                          int Ktrue, int ldw, int groups, int64_t src_gs, int64_t w_gs, int64_t dst_gs, bool slow,
@@ -1883,17 +1967,20 @@ static int launch_gather(const T* src, const T* w, T* dst, const T* addend, cons
   a.src_gs = src_gs;
   a.w_gs = w_gs;
   a.dst_gs = dst_gs;
-  a.tiles_m = cdiv(M, 128);
-  GatherPlan plan{N <= 64 ? 64 : 128, 0};
-  if (sizeof(T) == 2 && !slow) plan = plan_gather(M, N, a.ktiles, groups);
-  const bool narrow = plan.bn == 64;
-  if (plan.pipe != 1 || plan.bn == 256 || affine || (bn_partial && !bwd)) a.g.perm = 0;   // class-major rows: default pipeline, dgrad modes
-  a.tiles_n = cdiv(N, plan.bn);
+  BwdStats bs{nullptr, nullptr, nullptr, 0, 0, 0};
+  if (bwd) bs = *bwd;
+  const bool stats = bn_partial != nullptr;
+  const GatherForm form = gather_form(sizeof(T) == 2, g, M, N, Ktrue, ldw, groups, slow, stats, bwd != nullptr, affine,
+                                      addend != nullptr, bs.addend_s2 != 0, bs.y2 != nullptr);
+  a.tiles_m = form.tiles_m;
+  const bool narrow = form.bn == 64;
+  a.g.perm = form.perm;
+  a.tiles_n = form.tiles_n;
   dim3 grid(a.tiles_m * a.tiles_n, groups);
-  const int stages = plan.pipe == 5 ? 1 : (plan.pipe ? plan.pipe : (sizeof(T) == 2 ? 1 : 2));   // PIPE 5 = one stage too
-  size_t smem = (size_t)stages * (128 + plan.bn) * 128;
+  const int stages = form.pipe_lds == 5 ? 1 : (form.pipe_lds ? form.pipe_lds : (sizeof(T) == 2 ? 1 : 2));   // PIPE 5 = one stage too
+  size_t smem = (size_t)stages * (128 + form.bn) * 128;
   {   // the LDS-staged epilogue needs the C tile: bf16 rows padded by 16 B, fp32 rows unpadded
-    const size_t bn = plan.bn;
+    const size_t bn = form.bn;
     const size_t epi_bytes = 128 * (bn * sizeof(T) + (sizeof(T) == 2 ? 16 : 0));
     const size_t red_bytes = 2 * (16 / sizeof(T)) * 260 * 4;   // BN-sum reduction scratch: [2*VEC] planes of 260 floats
     if (smem < epi_bytes) smem = epi_bytes;
@@ -1912,13 +1999,6 @@ static int launch_gather(const T* src, const T* w, T* dst, const T* addend, cons
               (long)src_elems);
     return IEEE_ERR_UNSUPPORTED;
   }
-  const bool stats = bn_partial != nullptr;
-  if (stats && (slow || sizeof(T) != 2)) {
-    set_error(IEEE_ERR_UNSUPPORTED, "conv: fused BN statistics need the bf16 vector path");
-    return IEEE_ERR_UNSUPPORTED;
-  }
-  BwdStats bs{nullptr, nullptr, nullptr, 0, 0, 0};
-  if (bwd) bs = *bwd;
   if (tl_totals != nullptr) {      // armed by ieee_conv_next_bn_totals for this launch
     if (stats && bs.y2 == nullptr) {
       bs.tot = tl_totals; bs.tot_gs = tl_totals_gs; bs.tot_rep = tl_totals_rep; bs.tot_rs = tl_totals_gs * groups;
@@ -1928,23 +2008,13 @@ static int launch_gather(const T* src, const T* w, T* dst, const T* addend, cons
     tl_totals = nullptr;
     tl_totals_flag = nullptr;
   }
-  if (affine && slow) {
-    set_error(IEEE_ERR_UNSUPPORTED, "conv: the fused inference BatchNorm needs the vector path");
+  if (form.refuse != nullptr) {
+    set_error(IEEE_ERR_UNSUPPORTED, "%s", form.refuse);
     return IEEE_ERR_UNSUPPORTED;
   }
-  const int mode = affine ? 3 : ((stats && bwd) ? 2 : (stats ? 1 : 0));
-  if (bs.y2 != nullptr) {
-    // the second BatchNorm's sums exist as ONE instantiation (plain-row dgrad epilogue of the single-stage bf16 pipeline):
-    // force that pipeline, refuse the forms that have their own epilogue variants
-    if (!(sizeof(T) == 2 && !slow && mode == 2 && !a.g.perm && !bs.addend_s2 && plan.bn != 256 && !patch_eligible(a.g, M))) {
-      set_error(IEEE_ERR_UNSUPPORTED, "conv: the sums of a second BatchNorm need a plain bf16 dgrad (no stride-2 row order, no "
-                                      "compact addend, no 3x3 patch form)");
-      return IEEE_ERR_UNSUPPORTED;
-    }
-    plan.pipe = 1;
-  }
+  const int mode = form.mode;
   if constexpr (sizeof(T) == 2) {
-    if (!slow && stem_eligible(a.g, N, ldw, mode, addend)) {
+    if (form.family == 2) {
       // (a workgroup persistent over four tiles was measured in round 6 and lost: LABNOTES R6.3c)
       dim3 sgrid(a.tiles_m, groups);
       const size_t ssm = STEM_EPI_BYTES;   // staged epilogue (18 KB) > patch (11 KB) > BN-sum scratch
@@ -1953,22 +2023,14 @@ static int launch_gather(const T* src, const T* w, T* dst, const T* addend, cons
       else launch_timed(stem_conv_kernel<0>, sgrid, ssm, st, src, w, dst, (float*)nullptr, a, bs);
       return launch_status("stem_conv_kernel");
     }
-    if (!slow && plan.bn != 256 && !bs.addend_s2 && patch_eligible(a.g, M)) {
-      static const int f_style_env = getenv("IEEE_PATCH_STYLE") ? atoi(getenv("IEEE_PATCH_STYLE")) : -1;
-      static const int f_bn = getenv("IEEE_PATCH_BN") ? atoi(getenv("IEEE_PATCH_BN")) : 0;
-      const int bn = (N <= 64) ? 64 : (f_bn ? f_bn : plan.bn);
-      // measured per layer (scripts/experiments/scan_r3g.sh): the two-stage weight ring wins where the tile is 128 x 64 (39 KB of LDS keeps
-      // 4 workgroups per CU: 256->256 755 -> 923 TFLOP/s, 64->64 608 -> 650) and loses at 128 x 128 (55 KB -> 2 per CU:
-      // 512->512 1 320 -> 1 234, 128->128 871 -> 767)
-      const int f_style = f_style_env >= 0 ? f_style_env : (bn == 64 ? 0 : 1);
-      a.tiles_n = cdiv(N, bn);
+    if (form.family == 1) {
       dim3 pgrid(a.tiles_m * a.tiles_n, groups);
-      const int wlog = a.g.Ws == 8 ? 3 : (a.g.Ws == 16 ? 4 : 5);
-      if (bn == 64) {
-        if (f_style == 0) launch_patch_w<64, 0>(wlog, mode, pgrid, st, src, w, dst, addend, bn_partial, a, bs);
+      const int wlog = form.wlog;
+      if (form.bn == 64) {
+        if (form.style == 0) launch_patch_w<64, 0>(wlog, mode, pgrid, st, src, w, dst, addend, bn_partial, a, bs);
         else launch_patch_w<64, 1>(wlog, mode, pgrid, st, src, w, dst, addend, bn_partial, a, bs);
       } else {
-        if (f_style == 0) launch_patch_w<128, 0>(wlog, mode, pgrid, st, src, w, dst, addend, bn_partial, a, bs);
+        if (form.style == 0) launch_patch_w<128, 0>(wlog, mode, pgrid, st, src, w, dst, addend, bn_partial, a, bs);
         else launch_patch_w<128, 1>(wlog, mode, pgrid, st, src, w, dst, addend, bn_partial, a, bs);
       }
       return launch_status("conv3x3_patch_kernel");
@@ -1980,11 +2042,11 @@ static int launch_gather(const T* src, const T* w, T* dst, const T* addend, cons
   } else if constexpr (sizeof(T) == 2) {
 #define IEEE_GATHER_CASE(BN_, PIPE_) \
     launch_gather_mode<T, BN_, PIPE_>(mode, grid, smem, st, src, w, dst, addend, bn_partial, a, bs)
-    if (plan.bn == 256) {
-      if (plan.pipe == 1) IEEE_GATHER_CASE(256, 1);
+    if (form.bn == 256) {
+      if (form.pipe == 1) IEEE_GATHER_CASE(256, 1);
       else IEEE_GATHER_CASE(256, 0);
     } else if (narrow) {
-      switch (plan.pipe) {
+      switch (form.pipe) {
         case 1: IEEE_GATHER_CASE(64, 1); break;
         case 2: IEEE_GATHER_CASE(64, 2); break;
         case 3: IEEE_GATHER_CASE(64, 3); break;
@@ -1992,7 +2054,7 @@ static int launch_gather(const T* src, const T* w, T* dst, const T* addend, cons
         default: IEEE_GATHER_CASE(64, 0); break;
       }
     } else {
-      switch (plan.pipe) {
+      switch (form.pipe) {
         case 1: IEEE_GATHER_CASE(128, 1); break;
         case 5: IEEE_GATHER_CASE(128, 5); break;
         case 2: IEEE_GATHER_CASE(128, 2); break;
@@ -2039,6 +2101,52 @@ extern "C" int64_t ieee_conv_packed_ld(int dtype, int64_t inner_channels, int64_
   const int64_t K = R * S * inner_channels, bk = elem_bk(dtype);
   return (K + bk - 1) / bk * bk;
 }
+
+namespace {
+// the GEMM a forward / dgrad call is, as launch_gather takes it (shared by the entry points and ieee_conv_plan)
+struct ConvProblem {
+  GatherGeom g;
+  int M, N, Ktrue, ldw;
+  bool slow;
+};
+ConvProblem fwd_problem(const Dims& d, int dtype) {
+  ConvProblem p;
+  p.g = GatherGeom{d.Hi, d.Wi, d.Ci, d.Ho, d.Wo, d.R, d.S, d.stride, -d.pad, +1, 1, d.N * d.Ho * d.Wo};
+  const int bk = elem_bk(dtype), vec = elem_vec(dtype);
+  const int Ci = d.Ci, S = d.S, R = d.R, pad = d.pad, Wi = d.Wi, stride = d.stride;
+  // vector path: whole k-tiles per tap; or several whole taps per k-tile inside one filter row; or (Ci < one 16-byte
+  // chunk, no padding) chunks of vec/Ci horizontally adjacent pixels and k-tiles of whole filter rows -- see
+  // LoaderIm2colNT
+  const bool fast = (Ci % bk == 0) || (Ci < bk && Ci % vec == 0 && bk % Ci == 0 && S % (bk / Ci) == 0) ||
+                    (Ci < vec && vec % Ci == 0 && pad == 0 && (bk / Ci) % S == 0 && R % ((bk / Ci) / S) == 0 &&
+                     S % (vec / Ci) == 0 && Wi % (vec / Ci) == 0 && stride % (vec / Ci) == 0);
+  p.slow = !fast;
+  p.M = p.g.npix;
+  p.N = d.Co;
+  p.Ktrue = d.R * d.S * d.Ci;
+  p.ldw = (int)ieee_conv_packed_ld(dtype, d.Ci, d.R, d.S);
+  return p;
+}
+ConvProblem dgrad_problem(const Dims& d, int dtype) {
+  ConvProblem p;
+  // rows = input pixels; source = dY [N,Ho,Wo,Co]; h_dy = (hi + pad - r) / stride
+  p.g = GatherGeom{d.Ho, d.Wo, d.Co, d.Hi, d.Wi, d.R, d.S, 1, d.pad, -1, d.stride, d.N * d.Hi * d.Wi};
+  p.slow = false;
+  p.M = p.g.npix;
+  p.N = d.Ci;
+  p.Ktrue = d.R * d.S * d.Co;
+  p.ldw = (int)ieee_conv_packed_ld(dtype, d.Co, d.R, d.S);
+  if (dtype == IEEE_BF16) {
+    // stride 2: rows in parity-class-major order so that a workgroup skips the taps that cannot reach its pixels
+    static const bool f_perm = !(getenv("IEEE_DGRAD_PERM") && atoi(getenv("IEEE_DGRAD_PERM")) == 0);
+    // (3x3 only: for a 1x1 the skipped work is outweighed by the stride-2 scatter of the stores -- 140 -> 167 us alone)
+    if (f_perm && d.stride == 2 && d.R * d.S > 1 && !(d.Hi & 1) && !(d.Wi & 1) && ((d.Hi >> 1) * (d.Wi >> 1)) % 128 == 0 && 128 % (d.Wi >> 1) == 0 && d.Co % 64 == 0 && (int64_t)p.g.npix * d.Ci < (1ll << 31) &&
+        d.R * d.S <= 56)
+      p.g.perm = 1;
+  }
+  return p;
+}
+}  // namespace
 
 extern "C" int ieee_pack_conv_weight_padded(const float* w_oihw, void* dst, int dtype, int mode, int64_t groups,
                                             int64_t Co, int64_t Ci_src, int64_t R_src, int64_t S_src, int64_t Ci,
@@ -2115,24 +2223,14 @@ extern "C" int ieee_conv2d_fwd(const void* x, const void* w_packed, void* y, int
   Dims d;
   IEEE_TRY(check_dims("conv2d_fwd", N, Hi, Wi, Ci, Co, R, S, stride, pad, &d));
   IEEE_REQUIRE(Co % 4 == 0, "conv2d_fwd: Cout %ld must be a multiple of 4", (long)Co);
-  GatherGeom g{d.Hi, d.Wi, d.Ci, d.Ho, d.Wo, d.R, d.S, d.stride, -d.pad, +1, 1, d.N * d.Ho * d.Wo};
-  const int bk = elem_bk(dtype);
-  const int vec = elem_vec(dtype);
-  // vector path: whole k-tiles per tap; or several whole taps per k-tile inside one filter row; or (Ci < one 16-byte
-  // chunk, no padding) chunks of vec/Ci horizontally adjacent pixels and k-tiles of whole filter rows -- see
-  // LoaderIm2colNT
-  const bool fast = (Ci % bk == 0) || (Ci < bk && Ci % vec == 0 && bk % Ci == 0 && S % (bk / Ci) == 0) ||
-                    (Ci < vec && vec % Ci == 0 && pad == 0 && (bk / Ci) % S == 0 && R % ((bk / Ci) / S) == 0 &&
-                     S % (vec / Ci) == 0 && Wi % (vec / Ci) == 0 && stride % (vec / Ci) == 0);
-  const bool slow = !fast;
-  const int ldw = (int)ieee_conv_packed_ld(dtype, Ci, R, S);
+  const ConvProblem p = fwd_problem(d, dtype);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == IEEE_F32)
-    return launch_gather<float>((const float*)x, (const float*)w_packed, (float*)y, nullptr, g, g.npix, d.Co,
-                                d.R * d.S * d.Ci, ldw, (int)groups, x_gs, w_gs, y_gs, slow, st, bn_partial);
+    return launch_gather<float>((const float*)x, (const float*)w_packed, (float*)y, nullptr, p.g, p.M, p.N,
+                                p.Ktrue, p.ldw, (int)groups, x_gs, w_gs, y_gs, p.slow, st, bn_partial);
   if (dtype == IEEE_BF16)
-    return launch_gather<bf16>((const bf16*)x, (const bf16*)w_packed, (bf16*)y, nullptr, g, g.npix, d.Co,
-                               d.R * d.S * d.Ci, ldw, (int)groups, x_gs, w_gs, y_gs, slow, st, bn_partial);
+    return launch_gather<bf16>((const bf16*)x, (const bf16*)w_packed, (bf16*)y, nullptr, p.g, p.M, p.N,
+                               p.Ktrue, p.ldw, (int)groups, x_gs, w_gs, y_gs, p.slow, st, bn_partial);
   IEEE_REQUIRE(false, "conv2d_fwd: bad dtype %d", dtype);
 }
 
@@ -2145,20 +2243,15 @@ extern "C" int ieee_conv2d_fwd_bn_eval(const void* x, const void* w_packed, void
   Dims d;
   IEEE_TRY(check_dims("conv2d_fwd_bn_eval", N, Hi, Wi, Ci, Co, R, S, stride, pad, &d));
   IEEE_REQUIRE(Co % elem_vec(dtype) == 0, "conv2d_fwd_bn_eval: Cout %ld must be a multiple of %d", (long)Co, elem_vec(dtype));
-  GatherGeom g{d.Hi, d.Wi, d.Ci, d.Ho, d.Wo, d.R, d.S, d.stride, -d.pad, +1, 1, d.N * d.Ho * d.Wo};
-  const int bk = elem_bk(dtype), vec = elem_vec(dtype);
-  const bool fast = (Ci % bk == 0) || (Ci < bk && Ci % vec == 0 && bk % Ci == 0 && S % (bk / Ci) == 0) ||
-                    (Ci < vec && vec % Ci == 0 && pad == 0 && (bk / Ci) % S == 0 && R % ((bk / Ci) / S) == 0 &&
-                     S % (vec / Ci) == 0 && Wi % (vec / Ci) == 0 && stride % (vec / Ci) == 0);
-  const int ldw = (int)ieee_conv_packed_ld(dtype, Ci, R, S);
+  const ConvProblem p = fwd_problem(d, dtype);
   hipStream_t st = (hipStream_t)stream;
   BwdStats bs{nullptr, nullptr, bn_stats, out_gs, 4 * Co, relu};
   if (dtype == IEEE_F32)
-    return launch_gather<float>((const float*)x, (const float*)w_packed, (float*)out, (const float*)residual, g, g.npix,
-                                d.Co, d.R * d.S * d.Ci, ldw, (int)groups, x_gs, w_gs, out_gs, !fast, st, nullptr, &bs, true);
+    return launch_gather<float>((const float*)x, (const float*)w_packed, (float*)out, (const float*)residual, p.g, p.M,
+                                p.N, p.Ktrue, p.ldw, (int)groups, x_gs, w_gs, out_gs, p.slow, st, nullptr, &bs, true);
   if (dtype == IEEE_BF16)
-    return launch_gather<bf16>((const bf16*)x, (const bf16*)w_packed, (bf16*)out, (const bf16*)residual, g, g.npix, d.Co,
-                               d.R * d.S * d.Ci, ldw, (int)groups, x_gs, w_gs, out_gs, !fast, st, nullptr, &bs, true);
+    return launch_gather<bf16>((const bf16*)x, (const bf16*)w_packed, (bf16*)out, (const bf16*)residual, p.g, p.M, p.N,
+                               p.Ktrue, p.ldw, (int)groups, x_gs, w_gs, out_gs, p.slow, st, nullptr, &bs, true);
   IEEE_REQUIRE(false, "conv2d_fwd_bn_eval: bad dtype %d", dtype);
 }
 
@@ -2195,25 +2288,17 @@ extern "C" int ieee_conv2d_dgrad2(const void* dy, const void* w_packed_d, void* 
   IEEE_TRY(check_dims("conv2d_dgrad", N, Hi, Wi, Ci, Co, R, S, stride, pad, &d));
   IEEE_REQUIRE(Co % elem_bk(dtype) == 0, "conv2d_dgrad: Cout %ld must be a multiple of %d", (long)Co, elem_bk(dtype));
   IEEE_REQUIRE(Ci % 4 == 0, "conv2d_dgrad: Cin %ld must be a multiple of 4", (long)Ci);
-  // rows = input pixels; source = dY [N,Ho,Wo,Co]; h_dy = (hi + pad - r) / stride
-  GatherGeom g{d.Ho, d.Wo, d.Co, d.Hi, d.Wi, d.R, d.S, 1, d.pad, -1, d.stride, d.N * d.Hi * d.Wi};
-  const int ldw = (int)ieee_conv_packed_ld(dtype, Co, R, S);
+  const ConvProblem p = dgrad_problem(d, dtype);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == IEEE_F32)
-    return launch_gather<float>((const float*)dy, (const float*)w_packed_d, (float*)dx, (const float*)addend, g,
-                                g.npix, d.Ci, d.R * d.S * d.Co, ldw, (int)groups, dy_gs, w_gs, dx_gs, false, st);
+    return launch_gather<float>((const float*)dy, (const float*)w_packed_d, (float*)dx, (const float*)addend, p.g,
+                                p.M, p.N, p.Ktrue, p.ldw, (int)groups, dy_gs, w_gs, dx_gs, false, st);
   if (dtype == IEEE_BF16) {
-    // stride 2: rows in parity-class-major order so that a workgroup skips the taps that cannot reach its pixels
-    static const bool f_perm = !(getenv("IEEE_DGRAD_PERM") && atoi(getenv("IEEE_DGRAD_PERM")) == 0);
-    // (3x3 only: for a 1x1 the skipped work is outweighed by the stride-2 scatter of the stores -- 140 -> 167 us alone)
-    if (f_perm && d.stride == 2 && d.R * d.S > 1 && !(d.Hi & 1) && !(d.Wi & 1) && ((d.Hi >> 1) * (d.Wi >> 1)) % 128 == 0 && 128 % (d.Wi >> 1) == 0 && d.Co % 64 == 0 && (int64_t)g.npix * d.Ci < (1ll << 31) &&
-        d.R * d.S <= 56)
-      g.perm = 1;
     BwdStats bs{bn_y, bn_mask, bn_stats, dx_gs, 4 * Ci, 0, bn_mask_bits, addend_stride == 2 ? 1 : 0};
     bs.y2 = bn_y2;
     bs.partial2 = bn_partial2;
-    return launch_gather<bf16>((const bf16*)dy, (const bf16*)w_packed_d, (bf16*)dx, (const bf16*)addend, g, g.npix,
-                               d.Ci, d.R * d.S * d.Co, ldw, (int)groups, dy_gs, w_gs, dx_gs, false, st, bn_partial,
+    return launch_gather<bf16>((const bf16*)dy, (const bf16*)w_packed_d, (bf16*)dx, (const bf16*)addend, p.g, p.M,
+                               p.N, p.Ktrue, p.ldw, (int)groups, dy_gs, w_gs, dx_gs, false, st, bn_partial,
                                bn_partial ? &bs : nullptr);
   }
   IEEE_REQUIRE(false, "conv2d_dgrad: bad dtype %d", dtype);
@@ -2290,6 +2375,101 @@ static void fill_reduce_desc(ieee_wgrad_reduce_desc* o, const float* slab, float
   o->kind = kind; o->sl_log2 = sl_log2; o->blocks = blocks; o->accumulate = accumulate; o->block_begin = 0; o->reserved_ = 0;
 }
 
+// The form of ONE weight-gradient call: every choice wgrad_impl makes from the shape and the options of the call, made here
+// (host arithmetic only) so that the launcher and the plan query (ieee_conv_plan) cannot disagree.
+struct WgradForm {
+  int family = 0;                        // 0 conv_wgrad(_fold)_kernel (TN), 1 conv3x3_wgrad_patch_kernel, 2 stem_wgrad_kernel
+  int slow = 0, pipe = 0, half_m = 0, fold = 0, wlog = 0;
+  int nsplit = 1, kchunk = 0;            // of the kernel that runs (the patch form plans its own splits)
+  int tiles_n = 0, tiles = 0;            // TN: column tiles, tiles per (split, modality); patch: tiles = its 128 x 192 tiles
+  int lean = 0, xcd_group = 0, plain_x = 0, direct = 0;
+  int radix = 0, n1 = 0;                 // fold_plan of the splits in use (fold only)
+  int reduce = 0, sl_log2 = 0;           // slab reduction launch: 0 none, 1 vec4, 2 taps, 3 scalar
+  int64_t reduce_blocks = 0;             // its workgroups per modality
+};
+static WgradForm wgrad_form(int dtype, int64_t groups, const Dims& d, int accumulate, bool tickets, bool deferred, bool dw_ok,
+                            bool work_ok) {
+  WgradForm f;
+  const int64_t total = (int64_t)d.Co * d.Ci * d.R * d.S;
+  if (const int64_t ssplits = stem_wgrad_splits(dtype, d.N, d.Hi, d.Wi, d.Ho, d.Wo, d.Ci, d.Co, d.R, d.S, d.stride, d.pad)) {
+    // the stem: direct form over LDS patches (stem_wgrad_kernel), one slab per STEM_WG_ROWS output rows of an image
+    f.family = 2;
+    f.nsplit = (int)ssplits;
+    f.kchunk = STEM_WG_ROWS * d.Wo;
+    while (f.sl_log2 < 4 && (2 << f.sl_log2) <= ssplits && (total << f.sl_log2) * groups < (int64_t)256 * 2048) ++f.sl_log2;
+    f.reduce = 3;
+    f.reduce_blocks = cdiv(total, 256 >> f.sl_log2);
+    return f;
+  }
+  const int npix = d.N * d.Ho * d.Wo, ncols = d.R * d.S * d.Ci;
+  const int splitk = wgrad_splitk(npix, d.Co, ncols, groups, dtype, d.R * d.S);
+  const int bk = elem_bk(dtype);
+  f.kchunk = cdiv(cdiv(npix, splitk), bk) * bk;
+  f.nsplit = cdiv(npix, f.kchunk);
+  f.tiles_n = cdiv(ncols, 128);
+  f.tiles = cdiv(d.Co, 128) * f.tiles_n;
+  const int vec = elem_vec(dtype);
+  // a 16-byte chunk of im2col(X) is vec consecutive channels of one tap, or (Ci < vec, no padding) vec/Ci adjacent pixels
+  const bool chunk_ok = d.Ci % vec == 0 || (vec % d.Ci == 0 && d.pad == 0 && d.S % (vec / d.Ci) == 0 && d.Wi % (vec / d.Ci) == 0 &&
+                                            d.stride % (vec / d.Ci) == 0);
+  f.slow = chunk_ok ? 0 : 1;
+  f.plain_x = (d.R == 1 && d.S == 1 && d.stride == 1 && d.pad == 0) ? 1 : 0;
+  // (the lean loaders keep 32-bit byte offsets into dY [npix][Co] and, for the 1x1 form, X [npix][ncols]; larger
+  // operands take the pointer-form loaders)
+  f.lean = (npix % bk == 0 && d.Co >= 8 && ncols >= 8 && (int64_t)npix * d.Co * 2 < (1ll << 32) &&
+            (!f.plain_x || (int64_t)npix * ncols * 2 < (1ll << 32))) ? 1 : 0;
+  const int nkz = f.nsplit * (int)groups;
+  static const int f_map = getenv("IEEE_WGRAD_MAP") ? atoi(getenv("IEEE_WGRAD_MAP")) : 2;
+  f.xcd_group = (nkz >= 24 || nkz % 8 == 0) ? 1 : f_map;
+  // default: single-stage LDS-DMA (106 VGPRs -> 4 workgroups per CU): -6 % wgrad time over register staging at 3
+  static const int f_pipe = getenv("IEEE_WGRAD_PIPE") ? atoi(getenv("IEEE_WGRAD_PIPE")) : 1;
+  f.pipe = (dtype == IEEE_BF16 && !f.slow) ? f_pipe : 0;
+  // one split of a 1x1 conv: the "slab" IS the gradient (slab order [co][ci] = OIHW), so the GEMM writes it in place and no
+  // reduction pass runs (the two CIM convs: 2 x 50 MB written, read back and written again per step otherwise)
+  f.direct = (f.nsplit == 1 && d.R * d.S == 1 && !accumulate && dw_ok) ? 1 : 0;
+  const int64_t wsplits = wpatch_splits(dtype, d.N, d.Hi, d.Wi, d.Ci, d.Co, d.R, d.S, d.stride, d.pad, groups);
+  const bool wpatch = wsplits > 0;
+  // the split-K fold inside the launch (FoldArgs): bf16 LDS-DMA forms with 16-byte aligned slabs / gradient
+  {
+    const int ns = wpatch ? (int)wsplits : f.nsplit;
+    const int tiles = wpatch ? cdiv(d.Co, 128) * (d.Ci / 64) * 3 : f.tiles;
+    if (tickets && !deferred && dtype == IEEE_BF16 && !f.slow && (wpatch || f.pipe == 1) && !f.direct && ns >= 2 &&
+        ns <= FOLD_MAX_SPLITS && ncols % 4 == 0 && work_ok && dw_ok && (d.Co % 128 == 0 || d.Co == 64)) {
+      fold_plan(ns, &f.radix, &f.n1);
+      f.fold = ((int64_t)groups * tiles * (f.n1 + 1) <= FOLD_TICKET_WORDS) ? 1 : 0;
+    }
+  }
+  if (wpatch) {
+    const int64_t ktiles_all = npix / 64, per = (ktiles_all + wsplits - 1) / wsplits;
+    f.family = 1;
+    f.nsplit = (int)wsplits;
+    f.kchunk = (int)(per * 64);
+    f.tiles = cdiv(d.Co, 128) * (d.Ci / 64) * 3;
+    f.tiles_n = 0;
+    f.wlog = d.Wi == 8 ? 3 : (d.Wi == 16 ? 4 : 5);
+    f.half_m = d.Co == 64 ? 1 : 0;
+    f.lean = f.xcd_group = f.plain_x = 0;
+    f.pipe = 0;
+  } else if (dtype == IEEE_BF16 && !f.slow) {
+    f.half_m = ((f.fold || f.pipe == 1) && d.Co <= 64) ? 1 : 0;
+  }
+  if (f.direct || f.fold) return f;
+  const int64_t slab_gs = (int64_t)f.nsplit * d.Co * ncols;
+  const bool vec4 = d.R * d.S == 1 && (total & 3) == 0 && dw_ok && (slab_gs & 3) == 0 && work_ok;
+  // split lanes: enough blocks to fill the chip on the small-weight layers, no idle lanes on the few-split ones
+  const int64_t outs = vec4 ? total / 4 : total;
+  while (f.sl_log2 < 4 && (2 << f.sl_log2) <= f.nsplit && (outs << f.sl_log2) * groups < (int64_t)256 * 2048) ++f.sl_log2;
+  f.reduce_blocks = cdiv(outs, 256 >> f.sl_log2);
+  f.reduce = vec4 ? 1 : 3;
+  static const int f_taps = getenv("IEEE_WGRAD_REDUCE_TAPS") ? atoi(getenv("IEEE_WGRAD_REDUCE_TAPS")) : 16;
+  if (d.R * d.S > 1 && f.nsplit <= f_taps && d.Ci % 4 == 0 && (slab_gs & 3) == 0 && work_ok) {
+    f.reduce = 2;
+    f.sl_log2 = 0;
+    f.reduce_blocks = (int64_t)d.Co * cdiv(d.Ci, RT_CIB);
+  }
+  return f;
+}
+
 // defer != NULL: run the GEMM only and describe the slab reduction in *defer (kind 0: nothing left to do)
 static int wgrad_impl(const void* dy, const void* x, float* dw_oihw, void* work, int dtype, int64_t groups,
                       int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co, int64_t R, int64_t S,
@@ -2299,23 +2479,22 @@ static int wgrad_impl(const void* dy, const void* x, float* dw_oihw, void* work,
   Dims d;
   IEEE_TRY(check_dims("conv2d_wgrad", N, Hi, Wi, Ci, Co, R, S, stride, pad, &d));
   IEEE_REQUIRE(Co % elem_vec(dtype) == 0, "conv2d_wgrad: Cout must be a multiple of %d", elem_vec(dtype));
-  if (const int64_t ssplits = stem_wgrad_splits(dtype, N, Hi, Wi, d.Ho, d.Wo, Ci, Co, R, S, stride, pad)) {
-    // the stem: direct form over LDS patches (stem_wgrad_kernel), one slab per STEM_WG_ROWS output rows of an image
-    hipStream_t st = (hipStream_t)stream;
+  IEEE_REQUIRE(dtype == IEEE_F32 || dtype == IEEE_BF16, "conv2d_wgrad: bad dtype %d", dtype);
+  const WgradForm f = wgrad_form(dtype, groups, d, accumulate, tickets != nullptr, defer != nullptr,
+                                 (dw_gs & 3) == 0 && ((uintptr_t)dw_oihw & 15) == 0, ((uintptr_t)work & 15) == 0);
+  hipStream_t st = (hipStream_t)stream;
+  if (f.family == 2) {
     float* slab = (float*)work;
-    const int64_t slab_gs = ssplits * 64 * 256;
-    stem_wgrad_kernel<<<dim3((unsigned)ssplits, (unsigned)groups), 256, 12 * 1024 + 16 * 1024, st>>>(
+    const int64_t slab_gs = (int64_t)f.nsplit * 64 * 256;
+    stem_wgrad_kernel<<<dim3((unsigned)f.nsplit, (unsigned)groups), 256, 12 * 1024 + 16 * 1024, st>>>(
         (const bf16*)dy, (const bf16*)x, slab, d.Hi, d.Wi, d.Ho, dy_gs, x_gs, slab_gs);
     IEEE_TRY(launch_status("stem_wgrad_kernel"));
-    const int64_t total = (int64_t)d.Co * d.Ci * d.R * d.S;
-    int sl_log2 = 0;
-    while (sl_log2 < 4 && (2 << sl_log2) <= ssplits && (total << sl_log2) * groups < (int64_t)256 * 2048) ++sl_log2;
-    dim3 rgrid(cdiv(total, 256 >> sl_log2), (unsigned)groups);
+    dim3 rgrid((unsigned)f.reduce_blocks, (unsigned)groups);
     if (defer) {
-      fill_reduce_desc(defer, slab, dw_oihw, slab_gs, dw_gs, (int)ssplits, d.Co, d.Ci, d.R * d.S, 2, sl_log2, (int)rgrid.x, accumulate);
+      fill_reduce_desc(defer, slab, dw_oihw, slab_gs, dw_gs, f.nsplit, d.Co, d.Ci, d.R * d.S, 2, f.sl_log2, (int)rgrid.x, accumulate);
       return IEEE_OK;
     }
-    wgrad_reduce_kernel<1><<<rgrid, 256, 0, st>>>(slab, dw_oihw, (int)ssplits, d.Co, d.Ci, d.R * d.S, slab_gs, dw_gs, accumulate, sl_log2);
+    wgrad_reduce_kernel<1><<<rgrid, 256, 0, st>>>(slab, dw_oihw, f.nsplit, d.Co, d.Ci, d.R * d.S, slab_gs, dw_gs, accumulate, f.sl_log2);
     return launch_status("wgrad_reduce_kernel");
   }
   WgradArgs a;
@@ -2323,34 +2502,21 @@ static int wgrad_impl(const void* dy, const void* x, float* dw_oihw, void* work,
   a.Co = d.Co;
   a.ncols = d.R * d.S * d.Ci;
   a.npix = a.g.npix;
-  const int splitk = wgrad_splitk(a.npix, d.Co, a.ncols, groups, dtype, d.R * d.S);
-  const int bk = elem_bk(dtype);
-  a.kchunk = cdiv(cdiv(a.npix, splitk), bk) * bk;
-  const int nsplit = cdiv(a.npix, a.kchunk);
-  a.tiles_n = cdiv(a.ncols, 128);
-  a.tiles = cdiv(d.Co, 128) * a.tiles_n;
-  a.nsplit = nsplit;
+  a.kchunk = f.kchunk;
+  a.tiles_n = f.tiles_n;
+  a.tiles = f.tiles;
+  a.nsplit = f.nsplit;
   a.groups = (int)groups;
   a.dy_gs = dy_gs;
   a.x_gs = x_gs;
-  a.slab_gs = (int64_t)nsplit * d.Co * a.ncols;
-  const int vec = elem_vec(dtype);
-  // a 16-byte chunk of im2col(X) is vec consecutive channels of one tap, or (Ci < vec, no padding) vec/Ci adjacent pixels
-  const bool chunk_ok = Ci % vec == 0 || (vec % Ci == 0 && pad == 0 && S % (vec / Ci) == 0 && Wi % (vec / Ci) == 0 &&
-                                          stride % (vec / Ci) == 0);
-  const bool slow = !chunk_ok;
-  a.plain_x = (d.R == 1 && d.S == 1 && d.stride == 1 && d.pad == 0) ? 1 : 0;
-  // (the lean loaders keep 32-bit byte offsets into dY [npix][Co] and, for the 1x1 form, X [npix][ncols]; larger
-  // operands take the pointer-form loaders)
-  a.lean = (a.npix % bk == 0 && d.Co >= 8 && a.ncols >= 8 && (int64_t)a.npix * d.Co * 2 < (1ll << 32) &&
-            (!a.plain_x || (int64_t)a.npix * a.ncols * 2 < (1ll << 32))) ? 1 : 0;
-  const int nkz = nsplit * (int)groups;
-  static const int f_map = getenv("IEEE_WGRAD_MAP") ? atoi(getenv("IEEE_WGRAD_MAP")) : 2;
-  a.xcd_group = (nkz >= 24 || nkz % 8 == 0) ? 1 : f_map;
+  a.slab_gs = (int64_t)f.nsplit * d.Co * a.ncols;
+  a.plain_x = f.plain_x;
+  a.lean = f.lean;
+  a.xcd_group = f.xcd_group;
+  const bool slow = f.slow != 0, direct = f.direct != 0, fold = f.fold != 0, wpatch = f.family == 1;
+  const int pipe = f.pipe;
+  const int nkz = f.nsplit * (int)groups;
   dim3 grid((unsigned)(a.tiles * (a.xcd_group == 1 ? cdiv(nkz, 8) * 8 : nkz)));
-  // default: single-stage LDS-DMA (106 VGPRs -> 4 workgroups per CU): -6 % wgrad time over register staging at 3
-  static const int f_pipe = getenv("IEEE_WGRAD_PIPE") ? atoi(getenv("IEEE_WGRAD_PIPE")) : 1;
-  const int pipe = (dtype == IEEE_BF16 && !slow) ? f_pipe : 0;
   // IEEE_WGRAD_LDS: dynamic LDS of the weight-gradient kernels in KB (>= what they use): caps their workgroups per CU, i.e. how
   // much of every CU the low-priority stream may hold against the launch stream's kernels.  48 KB = 3 per CU instead of 4:
   // each weight gradient alone is a little slower (511 vs 515 TFLOP/s serialized), the step is 0.15 ms faster (15.31 -> 15.16,
@@ -2364,56 +2530,37 @@ static int wgrad_impl(const void* dy, const void* x, float* dw_oihw, void* work,
     (void)hipFuncSetAttribute((const void*)conv_wgrad_kernel<bf16, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
   }
-  hipStream_t st = (hipStream_t)stream;
   float* slab = (float*)work;
-  // one split of a 1x1 conv: the "slab" IS the gradient (slab order [co][ci] = OIHW), so the GEMM writes it in place and no
-  // reduction pass runs (the two CIM convs: 2 x 50 MB written, read back and written again per step otherwise)
-  const bool direct = nsplit == 1 && d.R * d.S == 1 && !accumulate && (dw_gs & 3) == 0 && ((uintptr_t)dw_oihw & 15) == 0;
   if (direct) {
     slab = dw_oihw;
     a.slab_gs = dw_gs;
   }
-  const int64_t wsplits = wpatch_splits(dtype, N, Hi, Wi, Ci, Co, R, S, stride, pad, groups);
-  const bool wpatch = wsplits > 0;
-  int nsplit_used = nsplit;
-  // the split-K fold inside the launch (FoldArgs): bf16 LDS-DMA forms with 16-byte aligned slabs / gradient
+  const int nsplit_used = f.nsplit;
   FoldArgs fa{};
-  bool fold = false;
-  {
-    const int ns = wpatch ? (int)wsplits : nsplit;
-    const int tiles = wpatch ? cdiv(d.Co, 128) * (d.Ci / 64) * 3 : a.tiles;
-    if (tickets != nullptr && defer == nullptr && dtype == IEEE_BF16 && !slow && (wpatch || pipe == 1) && !direct && ns >= 2 &&
-        ns <= FOLD_MAX_SPLITS && a.ncols % 4 == 0 && ((uintptr_t)slab & 15) == 0 && ((uintptr_t)dw_oihw & 15) == 0 &&
-        (dw_gs & 3) == 0 && (d.Co % 128 == 0 || d.Co == 64)) {
-      fold_plan(ns, &fa.radix, &fa.n1);
-      fa.nsplit = ns;
-      fa.tiles = tiles;
-      fold = (int64_t)groups * tiles * (fa.n1 + 1) <= FOLD_TICKET_WORDS;
-      fa.tickets = tickets;
-      fa.dw = dw_oihw;
-      fa.dw_gs = dw_gs;
-      fa.lvl1_gs = (int64_t)fa.n1 * d.Co * a.ncols;
-      fa.lvl1 = slab + (int64_t)groups * ns * d.Co * a.ncols;
-      fa.accumulate = accumulate;
-      fa.RS = d.R * d.S;
-      fa.Ci = d.Ci;
-    }
+  if (f.radix > 0) {      // (filled whenever the fold's preconditions held, as before; read by the fold kernels only)
+    fa.radix = f.radix;
+    fa.n1 = f.n1;
+    fa.nsplit = f.nsplit;
+    fa.tiles = f.tiles;
+    fa.tickets = tickets;
+    fa.dw = dw_oihw;
+    fa.dw_gs = dw_gs;
+    fa.lvl1_gs = (int64_t)fa.n1 * d.Co * a.ncols;
+    fa.lvl1 = slab + (int64_t)groups * f.nsplit * d.Co * a.ncols;
+    fa.accumulate = accumulate;
+    fa.RS = d.R * d.S;
+    fa.Ci = d.Ci;
   }
   if (wpatch) {
     WgradPatchArgs pa;
-    const int64_t ktiles_all = a.npix / 64, per = (ktiles_all + wsplits - 1) / wsplits;
-    nsplit_used = (int)wsplits;
-    a.kchunk = (int)(per * 64);
-    a.slab_gs = (int64_t)nsplit_used * d.Co * a.ncols;
-    const int nkz = nsplit_used * (int)groups;
     pa.Hm = d.Hi; pa.Ci = d.Ci; pa.Co = d.Co; pa.npix = a.npix; pa.kchunk = a.kchunk; pa.nsplit = nsplit_used; pa.groups = (int)groups;
     pa.nchunks = d.Ci / 64;
-    pa.tiles = cdiv(d.Co, 128) * pa.nchunks * 3;
+    pa.tiles = f.tiles;
     pa.ncols = a.ncols;
     pa.dy_gs = dy_gs; pa.x_gs = x_gs; pa.slab_gs = a.slab_gs;
     dim3 pgrid((unsigned)(pa.tiles * cdiv(nkz, 8) * 8));
-    const int wlog = d.Wi == 8 ? 3 : (d.Wi == 16 ? 4 : 5);
-    const bool half = d.Co == 64;
+    const int wlog = f.wlog;
+    const bool half = f.half_m != 0;
 #define IEEE_WP_CASE(W_) \
     if (half && fold) conv3x3_wgrad_patch_kernel<W_, true, true><<<pgrid, 256, std::max((size_t)(64 * 256 + WPatch<W_>::BYTES), f_lds), st>>>((const bf16*)dy, (const bf16*)x, slab, pa, fa); \
     else if (fold) conv3x3_wgrad_patch_kernel<W_, false, true><<<pgrid, 256, std::max((size_t)(64 * 256 + WPatch<W_>::BYTES), f_lds), st>>>((const bf16*)dy, (const bf16*)x, slab, pa, fa); \
@@ -2424,7 +2571,7 @@ static int wgrad_impl(const void* dy, const void* x, float* dw_oihw, void* work,
   } else if (dtype == IEEE_F32) {
     if (slow) conv_wgrad_kernel<float, true><<<grid, 256, smem, st>>>((const float*)dy, (const float*)x, slab, a);
     else conv_wgrad_kernel<float, false><<<grid, 256, smem, st>>>((const float*)dy, (const float*)x, slab, a);
-  } else if (dtype == IEEE_BF16) {
+  } else {
     if (slow) conv_wgrad_kernel<bf16, true><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a);
     else if (fold && d.Co <= 64) conv_wgrad_fold_kernel<true><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, fa);
     else if (fold) conv_wgrad_fold_kernel<false><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a, fa);
@@ -2434,24 +2581,13 @@ static int wgrad_impl(const void* dy, const void* x, float* dw_oihw, void* work,
     else if (pipe == 3) conv_wgrad_kernel<bf16, false, 3><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a);
     else if (pipe == 4) conv_wgrad_kernel<bf16, false, 4><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a);
     else conv_wgrad_kernel<bf16, false><<<grid, 256, smem, st>>>((const bf16*)dy, (const bf16*)x, slab, a);
-  } else {
-    IEEE_REQUIRE(false, "conv2d_wgrad: bad dtype %d", dtype);
   }
   IEEE_TRY(launch_status("conv_wgrad_kernel"));
   if (defer) fill_reduce_desc(defer, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0);
   if (direct || fold) return IEEE_OK;
-  const int64_t total = (int64_t)d.Co * d.Ci * d.R * d.S;
-  const bool vec4 = d.R * d.S == 1 && (total & 3) == 0 && (dw_gs & 3) == 0 && (a.slab_gs & 3) == 0 &&
-                    ((uintptr_t)dw_oihw & 15) == 0 && ((uintptr_t)slab & 15) == 0;
-  // split lanes: enough blocks to fill the chip on the small-weight layers, no idle lanes on the few-split ones
-  const int64_t outs = vec4 ? total / 4 : total;
-  int sl_log2 = 0;
-  while (sl_log2 < 4 && (2 << sl_log2) <= nsplit_used && (outs << sl_log2) * groups < (int64_t)256 * 2048) ++sl_log2;
-  dim3 rgrid(cdiv(outs, 256 >> sl_log2), (unsigned)groups);
-  static const int f_taps = getenv("IEEE_WGRAD_REDUCE_TAPS") ? atoi(getenv("IEEE_WGRAD_REDUCE_TAPS")) : 16;
-  if (d.R * d.S > 1 && nsplit_used <= f_taps && d.Ci % 4 == 0 && (a.slab_gs & 3) == 0 && ((uintptr_t)slab & 15) == 0) {
-    const int RS = d.R * d.S;
-    dim3 tgrid((unsigned)(d.Co * cdiv(d.Ci, RT_CIB)), (unsigned)groups);
+  const int RS = d.R * d.S;
+  if (f.reduce == 2) {
+    dim3 tgrid((unsigned)f.reduce_blocks, (unsigned)groups);
     if (defer && RS <= 9) {
       fill_reduce_desc(defer, slab, dw_oihw, a.slab_gs, dw_gs, nsplit_used, d.Co, d.Ci, RS, 3, 0, (int)tgrid.x, accumulate);
       return IEEE_OK;
@@ -2460,14 +2596,17 @@ static int wgrad_impl(const void* dy, const void* x, float* dw_oihw, void* work,
                                                                                     dw_gs, accumulate);
     return launch_status("wgrad_reduce_taps_kernel");
   }
+  const bool vec4 = f.reduce == 1;
+  const int sl_log2 = f.sl_log2;
+  dim3 rgrid((unsigned)f.reduce_blocks, (unsigned)groups);
   if (defer) {
-    fill_reduce_desc(defer, slab, dw_oihw, a.slab_gs, dw_gs, nsplit_used, d.Co, d.Ci, d.R * d.S, vec4 ? 1 : 2, sl_log2, (int)rgrid.x, accumulate);
+    fill_reduce_desc(defer, slab, dw_oihw, a.slab_gs, dw_gs, nsplit_used, d.Co, d.Ci, RS, vec4 ? 1 : 2, sl_log2, (int)rgrid.x, accumulate);
     return IEEE_OK;
   }
   if (vec4)
-    wgrad_reduce_kernel<4><<<rgrid, 256, 0, st>>>(slab, dw_oihw, nsplit_used, d.Co, d.Ci, d.R * d.S, a.slab_gs, dw_gs, accumulate, sl_log2);
+    wgrad_reduce_kernel<4><<<rgrid, 256, 0, st>>>(slab, dw_oihw, nsplit_used, d.Co, d.Ci, RS, a.slab_gs, dw_gs, accumulate, sl_log2);
   else
-    wgrad_reduce_kernel<1><<<rgrid, 256, 0, st>>>(slab, dw_oihw, nsplit_used, d.Co, d.Ci, d.R * d.S, a.slab_gs, dw_gs, accumulate, sl_log2);
+    wgrad_reduce_kernel<1><<<rgrid, 256, 0, st>>>(slab, dw_oihw, nsplit_used, d.Co, d.Ci, RS, a.slab_gs, dw_gs, accumulate, sl_log2);
   return launch_status("wgrad_reduce_kernel");
 }
 
@@ -2566,5 +2705,56 @@ extern "C" int ieee_conv_next_bn_totals(void* totals, int64_t group_stride, int 
   ieee::tl_totals_flag = totals != nullptr ? overflow : nullptr;
   ieee::tl_totals_gs = group_stride;
   ieee::tl_totals_rep = replicas;
+  return IEEE_OK;
+}
+
+/* Which form a call of this shape runs (include/ieee_amd.h): the launchers' own decision functions, no HIP call. */
+extern "C" int ieee_conv_plan(int op, int dtype, int64_t groups, int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co,
+                              int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t flags, int64_t* fields, int64_t nfields) {
+  IEEE_REQUIRE(fields && nfields > 0, "conv_plan: no room for the fields");
+  IEEE_REQUIRE(op >= IEEE_CONV_OP_FWD && op <= IEEE_CONV_OP_WGRAD, "conv_plan: bad op %d", op);
+  IEEE_REQUIRE(dtype == IEEE_F32 || dtype == IEEE_BF16, "conv_plan: bad dtype %d", dtype);
+  IEEE_REQUIRE(groups > 0, "conv_plan: non-positive group count");
+  Dims d;
+  IEEE_TRY(check_dims("conv_plan", N, Hi, Wi, Ci, Co, R, S, stride, pad, &d));
+  int64_t out[IEEE_PLAN_NFIELDS] = {0};
+  const bool sums = (flags & IEEE_PLAN_F_BN_SUMS) != 0, has_addend = (flags & IEEE_PLAN_F_ADDEND) != 0;
+  if (op == IEEE_CONV_OP_WGRAD) {
+    IEEE_REQUIRE(Co % elem_vec(dtype) == 0, "conv_plan: Cout must be a multiple of %d", elem_vec(dtype));
+    const WgradForm f = wgrad_form(dtype, groups, d, (flags & IEEE_PLAN_F_ACCUMULATE) ? 1 : 0, (flags & IEEE_PLAN_F_TICKETS) != 0,
+                                   (flags & IEEE_PLAN_F_DEFERRED) != 0, true, true);
+    out[IEEE_PLAN_FAMILY] = f.family; out[IEEE_PLAN_SLOW] = f.slow; out[IEEE_PLAN_PIPE] = f.pipe; out[IEEE_PLAN_WLOG] = f.wlog;
+    out[IEEE_PLAN_HALF_M] = f.half_m; out[IEEE_PLAN_FOLD] = f.fold; out[IEEE_PLAN_NSPLIT] = f.nsplit; out[IEEE_PLAN_KCHUNK] = f.kchunk;
+    out[IEEE_PLAN_LEAN] = f.lean; out[IEEE_PLAN_XCD_GROUP] = f.xcd_group; out[IEEE_PLAN_DIRECT] = f.direct;
+    out[IEEE_PLAN_RADIX] = f.fold ? f.radix : 0; out[IEEE_PLAN_N1] = f.fold ? f.n1 : 0;
+    out[IEEE_PLAN_REDUCE] = f.reduce; out[IEEE_PLAN_SL_LOG2] = f.sl_log2;
+    out[IEEE_PLAN_LOADER] = f.family == 0 ? (f.plain_x && !f.slow ? 0 : 1) : 0;
+    out[IEEE_PLAN_TILES_M] = cdiv(d.Co, 128); out[IEEE_PLAN_TILES_N] = f.tiles_n;
+  } else {
+    GatherForm f;
+    if (op == IEEE_CONV_OP_DGRAD) {
+      IEEE_REQUIRE(Co % elem_bk(dtype) == 0, "conv_plan: dgrad needs Cout %% %d == 0", elem_bk(dtype));
+      IEEE_REQUIRE(Ci % 4 == 0, "conv_plan: dgrad needs Cin %% 4 == 0");
+      const ConvProblem p = dgrad_problem(d, dtype);
+      // (the fp32 dgrad has no fused form: ieee_conv2d_dgrad2 drops the BatchNorm operands there)
+      const bool st = sums && dtype == IEEE_BF16;
+      f = gather_form(dtype == IEEE_BF16, p.g, p.M, p.N, p.Ktrue, p.ldw, (int)groups, p.slow, st, st, false, has_addend,
+                      st && (flags & IEEE_PLAN_F_ADDEND_S2) != 0, st && (flags & IEEE_PLAN_F_BN2) != 0);
+    } else {
+      IEEE_REQUIRE(Co % 4 == 0, "conv_plan: Cout must be a multiple of 4");
+      const ConvProblem p = fwd_problem(d, dtype);
+      const bool eval = op == IEEE_CONV_OP_FWD_BN_EVAL;
+      f = gather_form(dtype == IEEE_BF16, p.g, p.M, p.N, p.Ktrue, p.ldw, (int)groups, p.slow, sums && !eval, eval, eval,
+                      eval && has_addend, false, false);
+    }
+    if (f.refuse != nullptr) {
+      set_error(IEEE_ERR_UNSUPPORTED, "%s", f.refuse);
+      return IEEE_ERR_UNSUPPORTED;
+    }
+    out[IEEE_PLAN_FAMILY] = f.family; out[IEEE_PLAN_BN] = f.bn; out[IEEE_PLAN_PIPE] = f.pipe; out[IEEE_PLAN_MODE] = f.mode;
+    out[IEEE_PLAN_VAR] = f.var; out[IEEE_PLAN_SLOW] = f.slow; out[IEEE_PLAN_WLOG] = f.wlog; out[IEEE_PLAN_STYLE] = f.style;
+    out[IEEE_PLAN_LOADER] = f.loader; out[IEEE_PLAN_TILES_M] = f.tiles_m; out[IEEE_PLAN_TILES_N] = f.tiles_n;
+  }
+  for (int64_t i = 0; i < nfields && i < IEEE_PLAN_NFIELDS; ++i) fields[i] = out[i];
   return IEEE_OK;
 }

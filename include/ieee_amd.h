@@ -355,6 +355,50 @@ int ieee_conv2d_wgrad_deferred(const void* dy, const void* x, float* dw_oihw, vo
 int ieee_wgrad_reduce_batch(const ieee_wgrad_reduce_desc* device_descs, int64_t n, int64_t total_blocks, int64_t groups,
                             void* stream);
 
+/* Which kernel form a conv call of this shape runs, WITHOUT running it: host arithmetic only (no HIP call, works on a machine
+ * without a GPU), computed by the functions the launchers themselves call, so a test can assert "this shape runs that form" and
+ * notices a retune.  No reference counterpart (torch picks its own algorithms).  (Hi, Wi, Ci, Co, R, S, stride, pad) are the
+ * FORWARD conv's, as in the calls above.  Pointers are taken as 16-byte aligned, dw_gs as Co*Ci*R*S.
+ * op: which entry point; flags: the options of that call that change the choice. */
+#define IEEE_CONV_OP_FWD 0          /* ieee_conv2d_fwd(_ex) */
+#define IEEE_CONV_OP_FWD_BN_EVAL 1  /* ieee_conv2d_fwd_bn_eval */
+#define IEEE_CONV_OP_DGRAD 2        /* ieee_conv2d_dgrad(2, _ex) */
+#define IEEE_CONV_OP_WGRAD 3        /* ieee_conv2d_wgrad(_fold, _deferred) */
+#define IEEE_PLAN_F_BN_SUMS 1       /* bn_partial != NULL (forward: MODE 1, dgrad: MODE 2) */
+#define IEEE_PLAN_F_ADDEND_S2 2     /* dgrad: addend_stride == 2 */
+#define IEEE_PLAN_F_BN2 4           /* dgrad: bn_y2 / bn_partial2 given */
+#define IEEE_PLAN_F_TICKETS 8       /* wgrad: ieee_conv2d_wgrad_fold */
+#define IEEE_PLAN_F_DEFERRED 16     /* wgrad: ieee_conv2d_wgrad_deferred */
+#define IEEE_PLAN_F_ACCUMULATE 32   /* wgrad: accumulate = 1 */
+#define IEEE_PLAN_F_ADDEND 64       /* dgrad addend / eval residual != NULL */
+/* indices into fields[] (entries a family does not have are 0) */
+#define IEEE_PLAN_FAMILY 0          /* forward / dgrad: 0 gather, 1 3x3 patch, 2 direct stem; wgrad: 0 TN, 1 3x3 patch, 2 direct stem */
+#define IEEE_PLAN_BN 1              /* output-channel tile width: 64 / 128 / 256 */
+#define IEEE_PLAN_PIPE 2
+#define IEEE_PLAN_MODE 3            /* epilogue: 0 store(+addend), 1 BN sums, 2 masked gradient + BN-backward sums, 3 eval BN */
+#define IEEE_PLAN_VAR 4             /* 1 parity-class rows, 2 compact stride-2 addend, 3 second BatchNorm */
+#define IEEE_PLAN_SLOW 5            /* element-gather loaders */
+#define IEEE_PLAN_WLOG 6            /* patch forms: log2 of the map width */
+#define IEEE_PLAN_STYLE 7           /* patch forward / dgrad: 0 two weight stages, 1 one */
+#define IEEE_PLAN_LOADER 8          /* 0 plain 1x1 matrix, 1 im2col, 2 im2col over parity-class rows */
+#define IEEE_PLAN_TILES_M 9
+#define IEEE_PLAN_TILES_N 10
+#define IEEE_PLAN_HALF_M 11         /* wgrad: 64-row tile */
+#define IEEE_PLAN_FOLD 12           /* wgrad: split-K fold inside the launch */
+#define IEEE_PLAN_NSPLIT 13
+#define IEEE_PLAN_KCHUNK 14         /* pixels per split */
+#define IEEE_PLAN_LEAN 15           /* wgrad TN: clamped lean loaders */
+#define IEEE_PLAN_XCD_GROUP 16
+#define IEEE_PLAN_DIRECT 17         /* wgrad: one split written straight into dw */
+#define IEEE_PLAN_RADIX 18          /* fold: splits per level-0 group */
+#define IEEE_PLAN_N1 19             /* fold: level-0 groups (1 = one level) */
+#define IEEE_PLAN_REDUCE 20         /* slab reduction launch: 0 none, 1 vec4, 2 taps, 3 scalar */
+#define IEEE_PLAN_SL_LOG2 21
+#define IEEE_PLAN_NFIELDS 22
+/* writes min(nfields, IEEE_PLAN_NFIELDS) entries; IEEE_ERR_UNSUPPORTED (with ieee_last_error) where the call itself refuses */
+int ieee_conv_plan(int op, int dtype, int64_t groups, int64_t N, int64_t Hi, int64_t Wi, int64_t Ci, int64_t Co,
+                   int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t flags, int64_t* fields, int64_t nfields);
+
 
 /* ---- BatchNorm2d (+ residual, + ReLU) over NHWC maps [M][C] ------------------ */
 /* torch.nn.BatchNorm2d as the reference instantiates it (resnet.py:151,164-184;
