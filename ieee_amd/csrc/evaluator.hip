@@ -746,6 +746,16 @@ extern "C" int ieee_distmat_member_pairs(const float* x, int64_t rows, int64_t d
   return launch_status("distmat_member_pairs");
 }
 
+extern "C" int ieee_row_rinv(const float* x, int64_t rows, int64_t d, float* out, void* stream) {
+  IEEE_REQUIRE(rows >= 0 && rows < (1ll << 31) && d > 0 && d < (1ll << 31) && d % 4 == 0,
+               "row_rinv: rows %ld, feature dim %ld (a multiple of 4)", (long)rows, (long)d);
+  if (rows == 0) return IEEE_OK;
+  IEEE_REQUIRE(x && out, "row_rinv: null pointer");
+  IEEE_REQUIRE(((uintptr_t)x & 15) == 0, "row_rinv: rows not 16-byte aligned");
+  rownorm_kernel<float><<<cdiv(rows, 4), 256, 0, (hipStream_t)stream>>>(x, rows, (int)d, 1, out);
+  return launch_status("row_rinv");
+}
+
 static int split_terms(int64_t scheme) {
   return scheme == IEEE_SPLIT_BF16X3 ? 6 : (scheme == IEEE_SPLIT_BF16X2 || scheme == IEEE_SPLIT_F16X2) ? 3 : 0;
 }

@@ -55,6 +55,29 @@ def _check_rerank_from(rerank_from):
         raise ValueError("rerank_from must be 'matrices' or 'descriptors', got {!r}".format(rerank_from))
 
 
+_QE_DEFAULTS = dict(k=5, alpha=3, times=1, mode='both')      # ieee_amd.expansion.expand_descriptors's
+
+
+def _check_query_expansion(query_expansion):
+    """query_expansion is None / False (off), True (the defaults) or a dict with keys among k, alpha, times, mode
+    -> None, or the checked settings.  It runs on one rank."""
+    if query_expansion is None or query_expansion is False:
+        return None
+    if query_expansion is True:
+        query_expansion = {}
+    if not isinstance(query_expansion, dict) or set(query_expansion) - set(_QE_DEFAULTS):
+        raise ValueError('query_expansion must be None, False, True or a dict with keys among k, alpha, times, mode, '
+                         'got {!r}'.format(query_expansion))
+    from .expansion import check_expansion_args
+    qe = dict(_QE_DEFAULTS, **query_expansion)
+    qe = dict(zip(('k', 'alpha', 'times', 'mode'),
+                  check_expansion_args(qe['k'], qe['alpha'], qe['times'], qe['mode'], 'query_expansion')))
+    if ddp.world_size() > 1:
+        raise ValueError('query_expansion runs on one rank; over {} ranks every rank would repeat the whole '
+                         '(Q+G) x (Q+G) neighbour sweep'.format(ddp.world_size()))
+    return qe
+
+
 def _check_stream_eval(stream_eval, rerank, use_metric_cuhk03):
     """stream_eval is the Market1501 protocol on one rank, on plain distances"""
     if not stream_eval:
@@ -148,11 +171,12 @@ class Engine(object):
             start_eval=0, eval_freq=-1, test_only=False, dist_metric='euclidean', normalize_feature=False,
             visrank=False, visrank_topk=10, use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False,
             rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None, stream_eval=False,
-            rerank_formulation=None, rerank_from='matrices'):
+            rerank_formulation=None, rerank_from='matrices', query_expansion=None):
         """engine.py:126-232.  As in the reference there is NO evaluation or checkpoint after the last epoch (the
         `(epoch + 1) != max_epoch` guard, :216), and re-ranking applies to test_only runs (its docstring, :171-172;
         the in-loop test call does not pass it on, :217-225).  rerank: False, True (k-reciprocal) or 'gnn' (see test;
-        rerank_k1 / rerank_k2 / rerank_formulation belong to 'gnn' alone).  vistsne / vistsne_labels / stream_eval: see test."""
+        rerank_k1 / rerank_k2 / rerank_formulation belong to 'gnn' alone).  vistsne / vistsne_labels / stream_eval:
+        see test.  query_expansion: see test; like rerank it applies to test_only runs."""
         if visrank and not test_only:
             raise ValueError('visrank can be set to True only if test_only=True')
         if vistsne and not test_only:
@@ -161,11 +185,12 @@ class Engine(object):
         _check_formulation(rerank_formulation)
         _check_rerank_from(rerank_from)
         _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
+        query_expansion = _check_query_expansion(query_expansion)
         eval_args = dict(dist_metric=dist_metric, normalize_feature=normalize_feature, save_dir=save_dir,
                          use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, stream_eval=stream_eval)
         if test_only:
             self.test(rerank=rerank, rerank_k1=rerank_k1, rerank_k2=rerank_k2, rerank_formulation=rerank_formulation,
-                      rerank_from=rerank_from,
+                      rerank_from=rerank_from, query_expansion=query_expansion,
                       visrank=visrank, visrank_topk=visrank_topk, vistsne=vistsne, vistsne_labels=vistsne_labels, **eval_args)
             return
         began = time.time()
@@ -252,7 +277,7 @@ class Engine(object):
     # ---- evaluation ----------------------------------------------------------------------------------------------
     def test(self, dist_metric='euclidean', normalize_feature=False, visrank=False, visrank_topk=10, save_dir='',
              use_metric_cuhk03=False, ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7, vistsne=False,
-             vistsne_labels=None, stream_eval=False, rerank_formulation=None, rerank_from='matrices'):
+             vistsne_labels=None, stream_eval=False, rerank_formulation=None, rerank_from='matrices', query_expansion=None):
         """every target dataset in turn (engine.py:287-337); returns the last one's mAP like the reference.
         rerank: False; True = k-reciprocal re-ranking (engine.py:402-406); 'gnn' = GNN re-ranking
         (ieee_amd.rerank.gnn_distmat with rerank_k1, rerank_k2 and formulation=rerank_formulation -- None, 'dense', 'sparse'
@@ -269,11 +294,16 @@ class Engine(object):
         relabelled identities to draw; None draws random.sample(range(1, 30), 6) like the reference.
         stream_eval: the CMC / mAP (Market1501 protocol) without the [Q, G] distance matrix: the gallery's descriptors go by
         in slabs (ieee_amd.metrics.evaluate_rank_streamed), and the visrank figures come from search_topk.  Same numbers
-        and report.  ValueError with rerank, with use_metric_cuhk03 or over more than one rank."""
+        and report.  ValueError with rerank, with use_metric_cuhk03 or over more than one rank.
+        query_expansion (not in the reference): None / False = off; True or a dict with keys among k, alpha, times, mode =
+        ieee_amd.expansion.expand_descriptors on (qf, gf) after the optional normalize_feature step and before any
+        distance is formed (defaults k=5, alpha=3, times=1, mode='both').  It replaces the descriptors, so it combines with
+        stream_eval, every rerank setting and use_metric_cuhk03.  Anything else, or more than one rank, is a ValueError."""
         _check_rerank(rerank)
         _check_formulation(rerank_formulation)
         _check_rerank_from(rerank_from)
         _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
+        query_expansion = _check_query_expansion(query_expansion)
         self.set_model_mode('eval')
         mAP = 0.0
         for name, loaders in self.test_loader.items():
@@ -286,7 +316,8 @@ class Engine(object):
                                         use_metric_cuhk03=use_metric_cuhk03, ranks=ranks, rerank=rerank,
                                         rerank_k1=rerank_k1, rerank_k2=rerank_k2, vistsne=vistsne,
                                         vistsne_labels=vistsne_labels, stream_eval=stream_eval,
-                                        rerank_formulation=rerank_formulation, rerank_from=rerank_from)
+                                        rerank_formulation=rerank_formulation, rerank_from=rerank_from,
+                                        query_expansion=query_expansion)
             if self.writer is not None:
                 self.writer.add_scalar('Test/{}/rank1'.format(name), rank1, self.epoch)
                 self.writer.add_scalar('Test/{}/mAP'.format(name), mAP, self.epoch)
@@ -344,13 +375,14 @@ class Engine(object):
     def _evaluate(self, dataset_name='', query_loader=None, gallery_loader=None, dist_metric='euclidean',
                   normalize_feature=False, visrank=False, visrank_topk=10, save_dir='', use_metric_cuhk03=False,
                   ranks=[1, 5, 10, 20], rerank=False, rerank_k1=26, rerank_k2=7, vistsne=False, vistsne_labels=None,
-                  stream_eval=False, rerank_formulation=None, rerank_from='matrices'):
+                  stream_eval=False, rerank_formulation=None, rerank_from='matrices', query_expansion=None):
         """descriptors -> distance matrix -> CMC / mAP, printed like engine.py:339-441; returns (rank-1, mAP).
         stream_eval: no distance matrix, the gallery goes by in slabs (see test)"""
         _check_rerank(rerank)
         _check_formulation(rerank_formulation)
         _check_rerank_from(rerank_from)
         _check_stream_eval(stream_eval, rerank, use_metric_cuhk03)
+        query_expansion = _check_query_expansion(query_expansion)
         if visrank and ddp.world_size() > 1:
             raise RuntimeError('visrank needs the whole distance matrix, which a sharded evaluation over {} ranks never '
                                'forms: run engine.run(test_only=True, visrank=True) in one process on one GPU '
@@ -376,6 +408,10 @@ class Engine(object):
         if normalize_feature:
             say('Normalzing features with L2 norm ...')
             qf, gf = F.normalize(qf, p=2, dim=1), F.normalize(gf, p=2, dim=1)
+        if query_expansion is not None:     # replaces the descriptors, so every path below takes it unchanged
+            say('Applying query expansion (k={k}, alpha={alpha}, times={times}, mode={mode}) ...'.format(**query_expansion))
+            from .expansion import expand_descriptors
+            qf, gf = expand_descriptors(qf, gf, **query_expansion)
         say('Computing distance matrix with metric={} ...'.format(dist_metric))
         sharded = ddp.world_size() > 1 and not use_metric_cuhk03 and not rerank
         distmat = None

@@ -858,6 +858,35 @@ int ieee_gnn_sparse_cosine(const int64_t* rowptr, const int32_t* col, const floa
                            const int64_t* tptr, const int32_t* trow, const float* tval, int64_t Q, int64_t G, int64_t g0,
                            int64_t g1, float* out, int64_t ldo, void* stream);
 
+/* ---- query expansion / database augmentation (ieee_amd/expansion.py; not in the reference) ----------------------- */
+/* out[i] = 1 / max(|x_i|, 1e-12) for the rows of x [rows][d] fp32, contiguous, 16-byte aligned, d % 4 == 0: the row
+ * norm pass of ieee_sqeuclid_distmat with metric 1 (the same kernel, the same bits), F.normalize's clamp.  A zero row
+ * gives 1e12.  Anything else is IEEE_ERR_BAD_ARG before any launch; rows == 0 is a no-op. */
+int ieee_row_rinv(const float* x, int64_t rows, int64_t d, float* out, void* stream);
+/* The weights of neighbour lists as ieee_rank_topk_merge leaves them: for each of `count` places
+ *   idx < 0 (a padded place): w = 0;  alpha == 0: w = 1;  else w = s^alpha with s = fmaxf(1 - dist, 0) in fp32, formed by
+ *   alpha - 1 multiplications left to right (a NaN distance gives s = 0, as +inf does).
+ * 0 <= alpha <= 64, else IEEE_ERR_BAD_ARG before any launch; count == 0 is a no-op. */
+int ieee_expand_weights(const int32_t* idx, const float* dist, int64_t count, int64_t alpha, float* w, void* stream);
+/* out[i] = [self_rinv[i] * self_rows[i] +] sum_j (w[i][j] * rinv[idx[i][j]]) * src[idx[i][j]], i < n, j < k ascending,
+ * then with normalize != 0 out[i] *= 1 / max(|out[i]|, 1e-12) (a zero sum stays a zero row).  All fp32 on the device:
+ *   src [n_src][d] row stride ld_src;  rinv [n_src] or null (then the coefficient is w alone);
+ *   idx int32 / w fp32 [n][k], row stride ld_list;  self_rows [n][d] row stride ld_self or null, self_rinv [n] or
+ *   null (then the self row enters unscaled);  out [n][d] row stride ld_out.
+ * An index outside [0, n_src) -- -1 is the padding of the lists -- adds nothing and nothing is read through it;
+ * duplicates are summed as often as they occur.  Per output element the sum is ONE fp32 chain: the self term (a
+ * product), then one fma per kept entry in list order; the squares are summed in float64, per thread ascending and then
+ * in block_tree_sum's association.  One workgroup per row, no atomics, no workspace, no host sync: the same bits on
+ * every call, however the rows are divided over calls and whether the 16-byte or the scalar loads are used (16-byte:
+ * d % 4 == 0 and src, self_rows, out 16-byte aligned with strides that are multiples of 4).  Up to d = 4096 a row stays
+ * in registers; beyond, it is stored unscaled and scaled in a second pass over out.
+ * 1 <= k <= 1024, d >= 1, strides at least the row, out disjoint from src and from self_rows, else IEEE_ERR_BAD_ARG
+ * before any launch; n == 0 is a no-op, n_src == 0 (src may be null) leaves the self term. */
+int ieee_neighbour_sum(const float* src, int64_t ld_src, int64_t n_src, const float* rinv, const int32_t* idx,
+                       const float* w, int64_t ld_list, int64_t n, int64_t k, const float* self_rows,
+                       const float* self_rinv, int64_t ld_self, int64_t d, int normalize, float* out, int64_t ld_out,
+                       void* stream);
+
 /* ---- descriptor t-SNE (torchreid/engine/engine.py:463-490, showPointMultiModal) ---------------------------------- */
 /* Exact (dense, O(n^2)) t-SNE in 2 output dimensions, Student-t degree of freedom 1, what the reference gets from
  * sklearn.manifold.TSNE(n_components=2).  `batch` independent problems of the same n run per call, on a grid axis (the

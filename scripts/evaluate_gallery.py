@@ -7,7 +7,9 @@
 --cams cameras; --distractors: the share of gallery rows whose identity no query has.  The gallery stays on the host in
 pieces of --piece rows, so only one slab of it is on the device at a time.  Prints mAP and the CMC curve at --ranks, the
 device memory peak, and with --compare the same from compute_distance_matrix + evaluate_rank and whether the two are
-equal."""
+equal.  --qe-k K [--qe-alpha A --qe-times T --qe-mode both|query]: query expansion (ieee_amd.expansion.expand_descriptors)
+before a second evaluation, so the result is printed before and after it; mode 'both' holds the whole gallery on the
+device, mode 'query' leaves it in its host pieces."""
 import argparse
 import os
 import sys
@@ -29,6 +31,10 @@ def main():
     ap.add_argument("--ranks", default="1,5,10,20")
     ap.add_argument("--compare", action="store_true", help="also the two-step path on the whole matrix")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--qe-k", type=int, default=None, help="query expansion over the K nearest neighbours (off when not given)")
+    ap.add_argument("--qe-alpha", type=int, default=3)
+    ap.add_argument("--qe-times", type=int, default=1)
+    ap.add_argument("--qe-mode", default="both", choices=("both", "query"))
     args = ap.parse_args()
     shape = [int(v) for v in args.synthetic.split(",")]
     if len(shape) not in (2, 3) or min(shape) < 1:
@@ -71,6 +77,20 @@ def main():
         query, pieces, q_pids, g_pids, q_camids, g_camids, max_rank=args.max_rank, metric=args.metric, slab=args.slab,
         precision=args.precision))
     show("streamed", cmc, m_ap, peak)
+    if args.qe_k is not None:
+        from ieee_amd.expansion import expand_descriptors
+        qe = dict(k=args.qe_k, alpha=args.qe_alpha, times=args.qe_times, mode=args.qe_mode)
+        (query2, gallery2), peak_qe = peak_of(lambda: expand_descriptors(
+            query, torch.cat(pieces) if args.qe_mode == "both" else pieces, precision=args.precision, **qe))
+        print("query expansion: device memory peak {:.1f} MB".format(peak_qe / 1e6))
+        if args.qe_mode == "query" and args.metric != "cosine":
+            print("note: mode 'query' returns unit-length queries and the gallery as it is; unless the gallery is "
+                  "normalised too, rank with --metric cosine")
+        (cmc_qe, m_ap_qe), peak = peak_of(lambda: evaluate_rank_streamed(
+            query2, gallery2, q_pids, g_pids, q_camids, g_camids, max_rank=args.max_rank, metric=args.metric,
+            slab=args.slab, precision=args.precision))
+        show("streamed after query expansion (k={k}, alpha={alpha}, times={times}, mode={mode})".format(**qe), cmc_qe,
+             m_ap_qe, peak)
     if args.compare:
         (cmc2, m_ap2), peak2 = peak_of(lambda: evaluate_rank(
             compute_distance_matrix(query, torch.cat(pieces).cuda(), args.metric, args.precision), q_pids, g_pids, q_camids,
