@@ -58,4 +58,7 @@ def __getattr__(name):
     if name == "FeatureExtractor":
         from .feature_extractor import FeatureExtractor
         return FeatureExtractor
+    if name in ("dbscan", "dbscan_layout"):
+        from . import cluster
+        return getattr(cluster, name)
     raise AttributeError("module 'ieee_amd' has no attribute %r" % name)

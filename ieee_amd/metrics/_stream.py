@@ -131,6 +131,14 @@ class SlabDistances(object):
     def _prepare(self, rows):
         return _dist._pad8(rows.detach().to(self.device).to(self.cdt).contiguous())
 
+    def set_query(self, query_rows):
+        """Another query side of at most as many rows as the first: the distance buffer and the workspace stay, so a
+        driver that walks its rows block by block (cluster.py) allocates them once, not once per block."""
+        q = self._prepare(query_rows)
+        if self._buf is not None and q.shape[0] > self._buf.shape[0]:
+            self._buf = None
+        self.q = q
+
     def stage(self, rows):
         """rows [n, d], on the host or on the device -> (buf, ldd, n): buf[:, :n] holds the distances, row stride ldd.
         The next call overwrites them."""

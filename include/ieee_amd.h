@@ -887,6 +887,49 @@ int ieee_neighbour_sum(const float* src, int64_t ld_src, int64_t n_src, const fl
                        const float* self_rinv, int64_t ld_self, int64_t d, int normalize, float* out, int64_t ld_out,
                        void* stream);
 
+/* ---- DBSCAN clustering (ieee_amd/cluster.py; not in the reference) --------------------------------- */
+/* The neighbour relation of N points, R(i, j) iff i == j or D[i][j] <= thr or D[j][i] <= thr (fp32 compares of the
+ * stored values, a NaN is never a neighbour), as two CSR structures; D arrives buffer by buffer and nothing of size
+ * N x N is allocated.  Row pointers are int64 [N + 1], columns int32.  The caller owns all memory, forms the exclusive
+ * sums between a _count and its _fill, and runs the stages in the order below; everything on `stream`, no host sync.
+ * 1 <= N < 2^31 - 1, else IEEE_ERR_BAD_ARG before any launch, as for null pointers and ranges outside the N points.
+ *
+ * dist: one [rows][cols] fp32 buffer, row stride ldd >= cols, holding D[row0 + r][col0 + c].  _count adds to
+ * deg[row0 + r] (zero before the first buffer) the columns with dist <= thr, the point's own column skipped whatever
+ * it holds.  _fill writes their indices col0 + c, ascending, to col[rowptr[row] + cursor[row] ...] and advances
+ * cursor[row] (zero before the first buffer): with the buffers of a row visited in ascending column order every list
+ * of A is sorted.  Nothing is written at or beyond rowptr[row + 1] or cap.  One workgroup per buffer row, no atomics.
+ * 16-byte loads where dist is 16-byte aligned and ldd % 4 == 0, scalar loads otherwise: the same lists. */
+int ieee_cluster_eps_count(const float* dist, int64_t ldd, int64_t rows, int64_t cols, int64_t row0, int64_t col0,
+                           int64_t N, float thr, int64_t* deg, void* stream);
+int ieee_cluster_eps_fill(const float* dist, int64_t ldd, int64_t rows, int64_t cols, int64_t row0, int64_t col0,
+                          int64_t N, float thr, const int64_t* rowptr, int32_t* cursor, int32_t* col, int64_t cap,
+                          void* stream);
+/* The OR closure X: for every edge i -> j of A (sorted lists) without an edge j -> i, list j of X gains i.  _count adds
+ * to cnt[j] (zero before); _fill draws slots from cursor[j] (int32, zero before), so the order inside a list of X is
+ * arbitrary; nothing is written at or beyond xptr[j + 1] or cap.  A symmetric D gives no entry. */
+int ieee_cluster_mirror_count(const int64_t* rowptr, const int32_t* col, int64_t N, int64_t* cnt, void* stream);
+int ieee_cluster_mirror_fill(const int64_t* rowptr, const int32_t* col, int64_t N, const int64_t* xptr, int32_t* cursor,
+                             int32_t* xcol, int64_t cap, void* stream);
+/* core[u] = (1 + |A_u| + |X_u| >= min_samples), one byte each; f[u] = u, the first parent array.  min_samples >= 1. */
+int ieee_cluster_core(const int64_t* rowptr, const int64_t* xptr, int64_t N, int64_t min_samples, uint8_t* core,
+                      int32_t* f, void* stream);
+/* One hook-and-shortcut round over the core points: fnext = f (a copy), then for every core u and each of its core
+ * neighbours v in A_u and X_u, g = f[f[v]] lowers fnext[f[u]] and fnext[u], and f[f[u]] lowers fnext[u] (integer
+ * atomicMin).  Only f is read for a decision, so fnext is a function of f.  *changed (device int32, cleared by the
+ * call) ends as 1 iff fnext != f.  Repeat with the arrays swapped until it stays 0: then f[u] is the smallest core
+ * index of u's component for every core u.  f and fnext must be different arrays. */
+int ieee_cluster_cc_round(const int64_t* rowptr, const int32_t* col, const int64_t* xptr, const int32_t* xcol,
+                          const uint8_t* core, int64_t N, const int32_t* f, int32_t* fnext, int32_t* changed,
+                          void* stream);
+/* root[u] = 1 where u is core and f[u] == u, else 0 (int64: its exclusive sum is `number`, the cluster of root u). */
+int ieee_cluster_roots(const uint8_t* core, const int32_t* f, int64_t N, int64_t* root, void* stream);
+/* labels[u] = number[f[u]] for a core point; otherwise the smallest number[f[v]] over the core entries v of A_u and
+ * X_u, or -1 where there is none. */
+int ieee_cluster_labels(const int64_t* rowptr, const int32_t* col, const int64_t* xptr, const int32_t* xcol,
+                        const uint8_t* core, const int32_t* f, const int64_t* number, int64_t N, int64_t* labels,
+                        void* stream);
+
 /* ---- descriptor t-SNE (torchreid/engine/engine.py:463-490, showPointMultiModal) ---------------------------------- */
 /* Exact (dense, O(n^2)) t-SNE in 2 output dimensions, Student-t degree of freedom 1, what the reference gets from
  * sklearn.manifold.TSNE(n_components=2).  `batch` independent problems of the same n run per call, on a grid axis (the
